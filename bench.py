@@ -2,16 +2,21 @@
 """Benchmark: forward+backward Mpix/s of the MI355X Gaussian-splat rasterizer at 1080p, 1M Gaussians,
 SH degree 3 (BASELINE.json configs[1]), one training view per GPU.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, settles the clock, times the K steps and prints the line with the headline figure
+(value, ms_per_step); its other blocks are null.  --full adds every other leg described below (the per-stage pass and
+roofline, config3 / config4 / config5, the CPU baseline and parity).  --dump-outputs DIR writes the last timed step's
+outputs as DIR/<name>.npy (dump_outputs).
 
 A step = one view rendered through the public GaussianRasterizer API (forward, including its
 num_rendered host sync), full backward of fixed synthetic upstream gradients dL/dcolor and dL/dinvdepth
 (fed to autograd directly: the gradient of loss = <dL/dcolor, color> + <dL/dinvdepth, invdepth>), and -- for N > 1 --
 the RCCL all-reduce of every Gaussian gradient.
 
-N = 1 measures configs[1] (1M Gaussians); the line also carries, each timed on the GPU in the same run:
+N = 1 measures configs[1] (1M Gaussians); with --full the line also carries, each timed on the GPU in the same run:
   config3            configs[2]: LOD cut -> weights -> render_post lerp -> rasterize fwd+bwd -> lerp bwd on a
                      synthetic binary hierarchy over configs[1]'s 1M leaves (the example dataset is not available
                      offline), stages separately and inclusive (SURVEY 8(d));
@@ -24,8 +29,8 @@ N = 1 measures configs[1] (1M Gaussians); the line also carries, each timed on t
                      the reference's own float operation order.
 N > 1: view-data parallel, weak scaling -- each rank renders its own view of its own replica of the same 1M-Gaussian
 scene (--P overrides) and the gradients are all-reduced (RCCL over xGMI), so the per-GPU work equals the N = 1 line's
-and the driver's per-N values form one weak-scaling curve.  The line then also carries config4: configs[3] (4M
-Gaussians per replica, one view per GPU, the same exchange) timed on the same N ranks.
+and the driver's per-N values form one weak-scaling curve.  With --full the line then also carries config4:
+configs[3] (4M Gaussians per replica, one view per GPU, the same exchange) timed on the same N ranks, and config5.
 Inputs are synthetic (seeded), resident in HBM before timing starts.  Rank 0 prints one JSON line.
 """
 import argparse
@@ -426,6 +431,50 @@ def num_rendered(st, H, W, deg):
                                       rs.campos, False, False, True)[0])
 
 
+DUMP_MAX_PIXELS = 1920 * 1080  # a 1080p frame whole: 4 floats per pixel, 33.2 MB
+DUMP_MAX_ROWS = 50_000         # 63 floats per Gaussian (48 of them dL/dsh at SH degree 3), 12.6 MB
+
+
+def dump_outputs(out_dir, st, radii, seed=0):
+    """--dump-outputs: what the last timed step handed to its caller, as float32 <name>.npy files in out_dir: the
+    rendered image, the inverse depth, the radii, and the gradient of every rasterizer input (after the exchange
+    when there is one).  The whole set stays under 64 MB: images larger than DUMP_MAX_PIXELS are cut to a seeded
+    sample of their pixels, per-Gaussian arrays longer than DUMP_MAX_ROWS to a seeded sample of their rows (the same
+    rows in every array; sample_pixels.npy / sample_rows.npy hold the sorted indices, as float64).  The inputs are seeded, so
+    two builds run with the same arguments write the same entries of the same tensors."""
+    os.makedirs(out_dir, exist_ok=True)
+    rng = np.random.default_rng(seed)
+
+    def pick(n, cap):
+        if n <= cap:
+            return None
+        return torch.from_numpy(np.sort(rng.choice(n, cap, replace=False)))
+
+    means3D, scales, rots, opac, shs = st["params"]
+    images = dict(color=st["color"], invdepth=st["invd"])
+    rows = dict(radii=radii, dmean3D=means3D.grad, dmean2D=st["means2D"].grad, dopacity=opac.grad, dscale=scales.grad,
+                drot=rots.grad, dsh=shs.grad)
+    n_pix = st["color"].shape[-2] * st["color"].shape[-1]
+    pix, row = pick(n_pix, DUMP_MAX_PIXELS), pick(means3D.shape[0], DUMP_MAX_ROWS)
+    out = {}
+    for k, t in images.items():
+        t = t.detach()
+        out[k] = t if pix is None else t.reshape(-1, n_pix)[:, pix.to(t.device)]
+    for k, t in rows.items():
+        t = t.detach()
+        out[k] = t if row is None else t[row.to(t.device)]
+    if pix is not None:
+        out["sample_pixels"] = pix
+    if row is not None:
+        out["sample_rows"] = row
+    total = 0
+    for k, t in out.items():
+        a = np.ascontiguousarray(t.to(torch.float64 if k.startswith("sample_") else torch.float32).cpu().numpy())
+        total += a.nbytes
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    assert total <= 64_000_000, total
+
+
 def bench_config4_one_gpu(P, deg, W, H, dev, steps, warmup):
     """configs[3]'s per-GPU work (P Gaussians, one 1080p view, fwd+bwd) on one GPU with no exchange: the N = 1
     point against which the driver's N > 1 lines (same per-rank work plus the all-reduce) scale."""
@@ -678,9 +727,20 @@ def main():
                          "(the core clock's ramp under load); 0: none")
     ap.add_argument("--dry-run", action="store_true",
                     help="launch and join the ranks, print the line's rank fields, run no GPU work (launcher test)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every other leg: the per-stage timing pass and the roofline of the dominant kernel, "
+                         "config3 / config4 / config5, the CPU baseline and the parity checks against the oracle (the "
+                         "--no-* switches take single legs out again); without it only the headline steps are run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (image, inverse depth, radii and the "
+                         "gradients of every input) as DIR/<name>.npy, float32")
     args = ap.parse_args()
     if args.gpus < 1:
         sys.exit(f"bench.py: --gpus must be >= 1 (got {args.gpus})")
+    if args.steps < 1:
+        sys.exit(f"bench.py: --steps must be >= 1 (got {args.steps})")
+    if not args.full:
+        args.no_stage_timing = args.no_extras = args.no_cpu_baseline = True
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # --gpus N without a launcher: start N ranks as a child process (before anything touches the GPU) and exit
         # with its code, so the command cannot silently measure one rank
@@ -716,12 +776,8 @@ def main():
     params, exchange = st["params"], st["exchange"]
 
     for _ in range(args.warmup):
-        radii = step()
+        step()
     torch.cuda.synchronize()
-    # frame statistics for the algorithmic-byte model
-    with torch.no_grad():
-        V = int((radii > 0).sum().item())
-    nr = num_rendered(st, H, W, deg)
     # Per-stage breakdown from an untimed pass with events around every stage; the timed region below
     # then brackets only the dominant stage's kernel (each timed event is a queue barrier).
     breakdown, dom, stats = {}, None, {}
@@ -766,7 +822,7 @@ def main():
     for i in range(args.steps):
         if dom is not None and i == args.steps - K_EV:
             L.set_stage_timing(True, stages=[dom])
-        step(time_exchange=exchange is not None)
+        radii = step(time_exchange=exchange is not None)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -774,6 +830,12 @@ def main():
     if dom is not None:
         stats = L.stage_stats()
         L.set_stage_timing(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, st, radii)
+    # frame statistics for the algorithmic-byte model
+    with torch.no_grad():
+        V = int((radii > 0).sum().item())
+    nr = num_rendered(st, H, W, deg)
     exchange_report = None
     if world > 1:
         ar_ms = float(np.mean([a.elapsed_time(b) for a, b in st["ar_events"]])) if st["ar_events"] else 0.0
@@ -872,6 +934,7 @@ def main():
             "metric": "forward+backward Mpix/s at 1080p (1M Gaussians); grad max-abs-err vs ref",
             "value": round(value, 3), "unit": "Mpix/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4),
+            "full": args.full,
             # every untimed step before the timed ones: warm-up, the stage-timing pass and the clock settle (launch_plan)
             "untimed_steps": args.warmup + n_stage + settle,
             "clock": ("sustained: the timed steps follow untimed ones until the step time stops falling (the core "
@@ -888,7 +951,8 @@ def main():
             # steps in launch order (one launch of each rasterizer kernel per step), so a kernel trace of this run can be
             # cut into its phases (tools/summarize_profile.py timing.json): warm-up, the stage-timing pass, the timed
             # steps (the last `evented` of them bracket the dominant kernel with HIP events)
-            "launch_plan": dict(warmup=args.warmup, stage_timing=n_stage, settle=settle, timed=args.steps, evented=K_EV),
+            "launch_plan": dict(warmup=args.warmup, stage_timing=n_stage, settle=settle, timed=args.steps,
+                                evented=K_EV if dom is not None else 0),
         }
         print(json.dumps(line))
     if world > 1:

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Config #5's training step (train_post.py with Cache_SPTs, the alt rasterizer and the photometric loss) end to end
 on one MI355X, on a synthetic 2-chunk merged hierarchy (BASELINE config #5 names the example dataset, which is not
-available here).  The step itself is bench.py's config5 leg (bench_config5), which the default bench run reports;
+available here).  The step itself is bench.py's config5 leg (bench_config5), which `bench.py --full` reports;
 this wrapper runs it alone with other sizes.  Prints one JSON object."""
 import argparse
 import json
