@@ -5,21 +5,22 @@ import torch
 from hlgs_core import synthetic as S
 
 
-def settings_for(cam, sh_degree, device, do_depth=True, debug=False, hierarchy=None):
+def settings_for(cam, sh_degree, device, do_depth=True, debug=False, hierarchy=None, scale_modifier=1.0):
     from diff_gaussian_rasterization import GaussianRasterizationSettings
     e_i = torch.empty(0, dtype=torch.int32, device=device)
     e_f = torch.empty(0, dtype=torch.float32, device=device)
     h = hierarchy or {}
     return GaussianRasterizationSettings(
         image_height=cam["H"], image_width=cam["W"], tanfovx=cam["tanfovx"], tanfovy=cam["tanfovy"],
-        bg=cam["bg"].to(device), scale_modifier=1.0, viewmatrix=cam["viewmatrix"].to(device),
+        bg=cam["bg"].to(device), scale_modifier=scale_modifier, viewmatrix=cam["viewmatrix"].to(device),
         projmatrix=cam["projmatrix"].to(device), sh_degree=sh_degree, campos=cam["campos"].to(device),
         prefiltered=False, debug=debug, render_indices=h.get("render_indices", e_i),
         parent_indices=h.get("parent_indices", e_i), interpolation_weights=h.get("interpolation_weights", e_f),
         num_node_kids=h.get("num_node_kids", e_i), do_depth=do_depth)
 
 
-def gpu_render(scene, cam, do_depth=True, grads=None, use_colors=False, use_cov=False, device="cuda"):
+def gpu_render(scene, cam, do_depth=True, grads=None, use_colors=False, use_cov=False, device="cuda",
+               scale_modifier=1.0, debug=False):
     """Forward (+ backward when `grads` is given) through GaussianRasterizer on the GPU."""
     from diff_gaussian_rasterization import GaussianRasterizer
     t = lambda a: torch.tensor(np.ascontiguousarray(a), device=device, requires_grad=True)  # noqa: E731
@@ -36,7 +37,8 @@ def gpu_render(scene, cam, do_depth=True, grads=None, use_colors=False, use_cov=
     else:
         kw["scales"] = t(scene["scales"])
         kw["rotations"] = t(scene["rotations"])
-    rs = settings_for(cam, scene.get("sh_degree", 0), device, do_depth=do_depth)
+    rs = settings_for(cam, scene.get("sh_degree", 0), device, do_depth=do_depth, debug=debug,
+                      scale_modifier=scale_modifier)
     rast = GaussianRasterizer(rs)
     color, radii, invd = rast(means3D=means3D, means2D=means2D, opacities=opac, **kw)
     out = dict(color=color.detach().cpu().numpy(), radii=radii.cpu().numpy(), invdepth=invd.detach().cpu().numpy())
@@ -68,11 +70,13 @@ def binned(fr):
     return int((fr.ranges[:, 1].astype(np.int64) - fr.ranges[:, 0].astype(np.int64)).sum())
 
 
-def oracle_render(scene, cam, do_depth=True, grads=None, use_colors=False, use_cov=False, lib=False, drop_empty=False):
+def oracle_render(scene, cam, do_depth=True, grads=None, use_colors=False, use_cov=False, lib=False, drop_empty=False,
+                  scale_modifier=1.0):
     """lib: the oracle build (False: the serial reference of every parity check; "fma": the same source with FMA
     contraction, for build-to-build variance).  drop_empty: see drops_empty."""
     from oracle import oracle as O
-    sc = dict(means3D=scene["means3D"], opacities=scene["opacities"], sh_degree=scene.get("sh_degree", 0))
+    sc = dict(means3D=scene["means3D"], opacities=scene["opacities"], sh_degree=scene.get("sh_degree", 0),
+              scale_modifier=scale_modifier)
     if use_colors:
         sc["colors_precomp"] = scene["colors_precomp"]
     else:

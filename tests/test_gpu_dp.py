@@ -155,6 +155,19 @@ def test_colour_factored_sh_exchange(alt, overlap):
     the SH gradient and the exchange rebuilds it (hlgs_sh_grad_from_colour).  One view: every gradient bitwise the plain
     backward's.  Two views' rows rebuilt together: the average of the two views' SH (and dc) gradients.  overlap=True:
     the exchange joins any late SH-backward work before it reads this rank's colour row."""
+    _colour_factored_case(alt, overlap, 3)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("alt", [False, True])
+def test_colour_factored_sh_exchange_partial_degree(alt):
+    """The same exchange at active degree 1 on 16 stored rows (alt: dc + 15), as early training has them: the rebuilt
+    rows past the active degree are exactly zero, as the plain backward's are."""
+    _colour_factored_case(alt, False, 1)
+
+
+def _colour_factored_case(alt, overlap, D):
+    """D: the active SH degree of both the rasterizer settings and the rebuild; the scene stores 16 rows."""
     import ctypes as C
     from hlgs_core import _lib as L
     from hlgs_core.dp import FlatGradExchange
@@ -173,7 +186,7 @@ def test_colour_factored_sh_exchange(alt, overlap):
             return GaussianRasterizer(GaussianRasterizationSettings(
                 image_height=H, image_width=W, tanfovx=cam["tanfovx"], tanfovy=cam["tanfovy"],
                 bg=torch.zeros(3, device="cuda"), scale_modifier=1.0, viewmatrix=cam["viewmatrix"].cuda(),
-                projmatrix=cam["projmatrix"].cuda(), sh_degree=3, campos=cam["campos"].cuda(), prefiltered=False,
+                projmatrix=cam["projmatrix"].cuda(), sh_degree=D, campos=cam["campos"].cuda(), prefiltered=False,
                 debug=False, antialiasing=True))
         factor = dict(means=params[0], sh=params[5], dc=params[4])
     else:
@@ -181,7 +194,7 @@ def test_colour_factored_sh_exchange(alt, overlap):
         params = [t(sc["means3D"]), t(sc["scales"]), t(sc["rotations"]), t(sc["opacities"]), t(sc["shs"])]
 
         def rast(cam):
-            return GaussianRasterizer(settings_for(cam, 3, "cuda", do_depth=True))
+            return GaussianRasterizer(settings_for(cam, D, "cuda", do_depth=True))
         factor = dict(means=params[0], sh=params[4])
 
     def backward(cam):
@@ -217,13 +230,17 @@ def test_colour_factored_sh_exchange(alt, overlap):
     P = params[0].shape[0]
     rows = torch.stack(rows).contiguous()
     sh_p = params[5] if alt else params[4]
-    dsh = torch.empty_like(sh_p)
-    ddc = torch.empty_like(params[4]) if alt else None
+    dsh = torch.full_like(sh_p, float("nan"))  # the rebuild writes every row, inactive ones included
+    ddc = torch.full_like(params[4], float("nan")) if alt else None
     lib = L.load()
-    L.check(lib.hlgs_sh_grad_from_colour(P, 2, 3, sh_p.shape[1], L.VARIANT_ALT if alt else L.VARIANT_HIERARCHY,
+    L.check(lib.hlgs_sh_grad_from_colour(P, 2, D, sh_p.shape[1], L.VARIANT_ALT if alt else L.VARIANT_HIERARCHY,
                                          L.ptr(params[0].detach()), rows.data_ptr(), rows.data_ptr() + 16,
                                          rows.shape[1], 0.5, L.ptr(dsh), L.ptr(ddc) if alt else None, L.stream()))
     i_sh = 5 if alt else 4
     torch.testing.assert_close(dsh, 0.5 * (plain[0][i_sh] + plain[1][i_sh]), rtol=1e-6, atol=1e-7)
     if alt:
         torch.testing.assert_close(ddc, 0.5 * (plain[0][4] + plain[1][4]), rtol=1e-6, atol=1e-7)
+    active = (D + 1) ** 2 - (1 if alt else 0)  # rows of sh_p the active degree reads
+    assert sh_p.shape[1] == 16 - (1 if alt else 0)
+    assert torch.all(dsh[:, active:] == 0) and all(torch.all(pl[i_sh][:, active:] == 0) for pl in plain)
+    assert dsh[:, :active].abs().max() > 0

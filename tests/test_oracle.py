@@ -126,11 +126,16 @@ class _ClampST(torch.autograd.Function):
         return g
 
 
-def torch_render(sc, cam, fr, deg, alt=False, aa=True):
+def torch_render(sc, cam, fr, deg, alt=False, aa=True, scale_modifier=1.0):
     """Differentiable float64 forward with the reference's semantics; the per-tile sorted lists come from
     the oracle frame (the sort itself has no gradient).  alt=True: the alt rasterizer's forward (AA scaling
     only when `aa`) with its backward's two departures from autograd modelled explicitly -- the clamp
-    gradient passes through, and the T_final * bg term enters dL/dalpha twice (backward.cu:608, 619)."""
+    gradient passes through, and the T_final * bg term enters dL/dalpha twice (backward.cu:608, 619).
+
+    scale_modifier: the covariance is built from the effective scale eff = scale_modifier * scales, returned as
+    out["eff"] with its gradient retained (the reference's dL_dscale is the gradient of eff, DESIGN A-23).
+    sc["shs"] may hold more rows than the (deg + 1)^2 active ones (alt: (deg + 1)^2 - 1 rest rows): _sh_rgb indexes
+    rows 0 .. (deg + 1)^2 - 1 only, so the inactive rows never enter the graph and autograd gives them exactly 0."""
     dt = torch.float64
     leaf = lambda a: torch.tensor(np.asarray(a, np.float64), dtype=dt, requires_grad=True)  # noqa: E731
     P = sc["means3D"].shape[0]
@@ -160,7 +165,9 @@ def torch_render(sc, cam, fr, deg, alt=False, aa=True):
         torch.stack([1 - 2 * (y * y + z * z), 2 * (x * y - r * z), 2 * (x * z + r * y)], -1),
         torch.stack([2 * (x * y + r * z), 1 - 2 * (x * x + z * z), 2 * (y * z - r * x)], -1),
         torch.stack([2 * (x * z - r * y), 2 * (y * z + r * x), 1 - 2 * (x * x + y * y)], -1)], -2)
-    Sig = Rs @ torch.diag_embed(scales ** 2) @ Rs.transpose(1, 2)
+    eff = scale_modifier * scales
+    eff.retain_grad()
+    Sig = Rs @ torch.diag_embed(eff ** 2) @ Rs.transpose(1, 2)
     A = view[:3, :3].T  # linear part of the view transform acting on column vectors
     tz = tview[:, 2]
     limx, limy = 1.3 * cam["tanfovx"], 1.3 * cam["tanfovy"]
@@ -218,7 +225,7 @@ def torch_render(sc, cam, fr, deg, alt=False, aa=True):
         hh, ww = len(ys), len(xs)
         color[:, ty0:ty0 + hh, tx0:tx0 + ww] = col.T.reshape(3, hh, ww)
         inv[0, ty0:ty0 + hh, tx0:tx0 + ww] = dep.reshape(hh, ww)
-    out = dict(color=color, invdepth=inv, means=means, scales=scales, rots=rots, opac=opac, shs=shs, ndc=ndc)
+    out = dict(color=color, invdepth=inv, means=means, scales=scales, eff=eff, rots=rots, opac=opac, shs=shs, ndc=ndc)
     if alt:
         out["dc"] = dc_l
     return out
@@ -339,6 +346,61 @@ def test_alt_oracle_matches_float64_autograd(P, deg, W, H, bg, aa, realcam):
         assert e < 2e-3, f"{name}: alt oracle vs autograd rel err {e}"
     e = _rel(gr["dmean2D"][vis, :2], tr["ndc"].grad.numpy()[vis])
     assert e < 2e-3, f"dmean2D: {e}"
+
+
+@pytest.mark.parametrize("alt,aa,mod,rows_deg,D,realcam,W,H,bg", [
+    (False, True, 1.7, 3, 1, 0, 64, 48, (0.0, 0.0, 0.0)),
+    (False, True, 0.5, 3, 0, 5, 60, 44, (0.3, 0.2, 0.1)),
+    (False, True, 2.5, 3, 2, 3, 52, 36, (0.0, 0.0, 0.0)),
+    (False, True, 1.7, 2, 1, 7, 48, 40, (0.2, 0.5, 0.8)),
+    (True, True, 1.7, 3, 1, 3, 64, 48, (0.2, 0.4, 0.6)),
+    (True, False, 0.5, 3, 0, 7, 48, 40, (0.0, 0.0, 0.0)),
+    (True, True, 2.5, 2, 1, 0, 60, 44, (0.0, 0.0, 0.0)),
+    (True, False, 2.5, 3, 2, 5, 52, 36, (0.6, 0.3, 0.2))])
+def test_oracle_scale_modifier_and_partial_degree(alt, aa, mod, rows_deg, D, realcam, W, H, bg):
+    """scale_modifier != 1 and an active SH degree D below the stored (rows_deg + 1)^2 rows, hierarchy and alt
+    rasterizer, on the reference's own cameras, against float64 autograd with the same modifier and degree.
+
+    dscale is compared with the gradient of the effective scale eff = scale_modifier * scales, not of `scales`:
+    computeCov3D's backward sets s = mod * scale (hierarchy-rasterizer backward.cu:347, alt-rasterizer
+    backward.cu:345), carries s through dL_drot, and returns dL_dscale = dot(Rt[i], dL_dMt[i]) without mod
+    (backward.cu:375-377 and :373-375).  So the returned dscale is dL/d(mod * scale) = (dL/dscale) / mod
+    (DESIGN A-23); compared with autograd's scales.grad it is off by a relative 1 - 1/mod.
+    The SH rows past the active degree get exactly 0, from the oracle and from autograd."""
+    cam = real_camera_small(realcam, W, H, bg=bg)
+    P = 250
+    sc = S.make_gaussians(P, rows_deg, cam, seed=P + 10 * D + rows_deg)
+    sc["sh_degree"] = D
+    sc["scale_modifier"] = mod
+    if alt:
+        sc = alt_scene(sc, aa)
+        sc["opacities"][: P // 10] = 0.999
+    fr = O.forward(sc, S.cam_numpy(cam))
+    g, gd = S.upstream_grads(W, H)
+    gr = O.backward(fr, sc, g, gd)
+    tr = torch_render(sc, cam, fr, D, alt=alt, aa=aa, scale_modifier=mod)
+    tol = _fwd_tol_far(cam, sc)
+    assert _rel(fr.color, tr["color"].detach().numpy()) < tol
+    assert _rel(fr.invdepth, tr["invdepth"].detach().numpy()) < tol
+    loss = (tr["color"] * torch.tensor(g, dtype=torch.float64)).sum() + \
+        (tr["invdepth"] * torch.tensor(gd, dtype=torch.float64)).sum()
+    loss.backward()
+    vis = fr.radii > 0
+    assert vis.sum() > P // 4
+    checks = [("dmean3D", tr["means"].grad), ("dscale", tr["eff"].grad), ("drot", tr["rots"].grad),
+              ("dopacity", tr["opac"].grad), ("dsh", tr["shs"].grad)]
+    if alt:
+        checks.append(("ddc", tr["dc"].grad))
+    for name, ref in checks:
+        e = _rel(gr[name][vis], ref.numpy()[vis])
+        assert e < 2e-3, f"{name}: oracle vs autograd rel err {e}"
+    e = _rel(gr["dmean2D"][vis, :2], tr["ndc"].grad.numpy()[vis])
+    assert e < 2e-3, f"dmean2D: {e}"
+    active = (D + 1) ** 2 - (1 if alt else 0)  # rows of `shs` the active degree reads
+    assert gr["dsh"].shape[1] == (rows_deg + 1) ** 2 - (1 if alt else 0) > active
+    assert np.all(gr["dsh"][:, active:] == 0) and np.all(tr["shs"].grad.numpy()[:, active:] == 0)
+    if active:
+        assert np.abs(gr["dsh"][:, :active]).max() > 0
 
 
 def test_alt_oracle_culls_tiles_and_renders_bg_when_empty():
