@@ -21,7 +21,8 @@ namespace hlgs {
 static std::atomic<int> g_entry_packing{1};       // hlgs_set_entry_packing
 static std::atomic<int> g_drop_empty{1};          // hlgs_set_drop_empty
 static std::atomic<uint32_t> g_plan_polls{kPlanPolls};  // hlgs_set_plan_polls
-bool pack_entries(int P) { return g_entry_packing.load(std::memory_order_relaxed) && P < (1 << (32 - kEntryShift)); }
+static bool pack_entries_fit(int P) { return P < (1 << (32 - kEntryShift)); }
+bool pack_entries(int P) { return g_entry_packing.load(std::memory_order_relaxed) && pack_entries_fit(P); }
 bool drop_empty(int P) { return g_drop_empty.load(std::memory_order_relaxed) && pack_entries(P); }
 FrameOpts frame_opts(int P)
 {
@@ -31,73 +32,6 @@ FrameOpts frame_opts(int P)
     o.polls = g_plan_polls.load(std::memory_order_relaxed);
     return o;
 }
-void launch_preprocess(const hlgs_raster_args& a, const Geom& g, int* radii, uint32_t* tile_count, int gx, int gy,
-                       const ZeroJob& z,
-                       hipStream_t s);
-void launch_tile_ranges(const Img& im, int T, const uint32_t* point_offsets, int P, uint32_t flags, hipStream_t s);
-void launch_plan(int P, const Geom& g, const Img& im, int gx, int gy, uint32_t* host, uint32_t seq, hipStream_t s,
-                 bool fused);
-bool lds_binning(int P, int gx, int gy);
-uint32_t* bin_histogram(const Img& im, int P, int gx, int gy);
-void launch_count_tiles(int P, const int* radii, const Geom& g, const Img& im, int gx, int gy, bool alt,
-                        hipStream_t s, uint32_t* hist, bool fused);
-void launch_binning(const hlgs_raster_args& a, const int* radii, const Geom& g, const Img& im, const Bin& b, int gx,
-                    int gy, uint32_t max_count, hipStream_t s, bool timing, Guard gd);
-void launch_blend_fwd(const hlgs_raster_args& a, const Geom& g, const Img& im, const Bin& b, int gx, int gy,
-                      float* out_color, float* out_invdepth, int* seen, hipStream_t s, Guard gd);
-void launch_blend_bwd(const hlgs_raster_args& a, const Geom& g, const Img& im, const Bin& b, const BwdScratch& rs,
-                      int gx, int gy, const float* dL_dpix, const float* dL_dinv, hipStream_t s);
-void launch_gauss_bwd(const hlgs_raster_args& a, const int* radii, const Geom& g, const BwdScratch& rs,
-                      const hlgs_grads& o, bool has_depth, hipStream_t s, hipStream_t late, hipEvent_t ev,
-                      const uint32_t* misc);
-void launch_mark_visible(int P, const float* means, const float* view, uint8_t* present, hipStream_t s);
-void launch_sh_from_colour(int P, int V, int D, int M, bool alt, const float* means, const float* campos,
-                           const float* drgb, int64_t stride, float scale, float* dsh, float* ddc, hipStream_t s);
-void launch_relocation(int P, const float* oo, const float* so, const int* N, const float* binoms, int n_max,
-                       float* on, float* sn, hipStream_t s);
-size_t ssim_partials(int C, int H, int W);
-void launch_ssim_forward(int C, int H, int W, const float* img1, const float* img2, int valid, float* abc,
-                         float* partial, float* out, hipStream_t s, bool clamp1);
-void launch_ssim_backward(int C, int H, int W, const float* img1, const float* img2, const float* abc,
-                          const float* coef, float* grad1, hipStream_t s, bool clamp1);
-int depth_l1_blocks(long n);
-void launch_depth_l1_forward(long n, const float* inv, const float* mono, const float* mask, float* partial,
-                             float* out, hipStream_t s);
-void launch_depth_l1_backward(long n, const float* inv, const float* mono, const float* mask, const float* coef,
-                              float* grad, hipStream_t s);
-void launch_upper_cut(const CutArgs& a, hipStream_t s);
-void launch_upper_cut_flat(const CutArgs& a, const int* order, hipStream_t s);
-void launch_rows(bool gather, long n, int row_bytes, const int64_t* idx, const void* src, void* dst, hipStream_t s);
-void launch_act_fwd(int64_t n, const float* op_raw, const float* sc_raw, const float* rot_raw, float* op, float* sc,
-                    float* rot, hipStream_t s);
-void launch_act_bwd(int64_t n, const float* op, const float* sc, const float* rot_raw, const float* g_op,
-                    const float* g_sc, const float* g_rot, float* d_op, float* d_sc, float* d_rot, hipStream_t s);
-void launch_morton(int P, const float* xyz, const float* mn, const float* mx, int64_t* codes, hipStream_t s);
-void launch_adam(float* param, const float* grad, float* m, float* v, const uint8_t* vis, float lr, float b1, float b2,
-                 float eps, uint32_t N, uint32_t M, hipStream_t s);
-void launch_expand_dynamic(int N, float target, const int* nodes, const float* pos, const float* scales,
-                           const float* vp, const float* vd, int* ri, int* pi, int* ni, uint32_t* counts,
-                           uint32_t* incl, uint32_t* tmp, hipStream_t s);
-void launch_weights_dynamic(int n, const int* idx, float target, const int* nodes, const float* pos,
-                            const float* scales, const float* vp, float* ts, int* kids, hipStream_t s);
-void launch_expand_static(int N, float target, const int* nodes, const float* boxes, const float* vp, int* ri,
-                          int* pi, int* ni, uint32_t* counts, uint32_t* incl, uint32_t* tmp, hipStream_t s);
-void launch_weights_static(int n, const int* idx, float target, const int* nodes, const float* boxes,
-                           const float* vp, float* ts, int* kids, hipStream_t s);
-void launch_spt_prepare(int s_, const int* starts, const float* smax, const int* sidx, const float* sdist,
-                        uint32_t* sizes, uint32_t* incl, uint32_t* tmp, hipStream_t s);
-void launch_spt_finish(int s_, int E, int n, const int* gidx, const int* starts, const float* smin, const int* sidx,
-                       const float* sdist, int compat, const uint32_t* sizes, const uint32_t* incl, uint32_t* counts,
-                       uint32_t* counts_incl, uint32_t* tmp_s, int* result, uint32_t* keep, uint32_t* keep_incl,
-                       uint32_t* tmp_n, int* cut, int* counts_prefix, hipStream_t s);
-void launch_lod_interp_fwd(int S, int n, int M3, const int* ridx, const int* pidx, const float* w, const float* means,
-                           const float* scales, const float* rots, const float* opac, const float* shs, float* om,
-                           float* osc, float* orot, float* oop, float* osh, hipStream_t s);
-size_t lerp_bwd_scratch_elems(int P, int n);
-void launch_lod_interp_bwd(int P, int S, int n, int M3, const int* ridx, const int* pidx, const float* w,
-                           const float* rots, const float* gm, const float* gsc, const float* grot, const float* gop,
-                           const float* gsh, float* dm, float* dsc, float* drot, float* dop, float* dsh, void* scratch,
-                           hipStream_t s);
 
 // ---------------------------------------------------------------- buffer carving
 template <typename T>
@@ -196,8 +130,6 @@ static int check_stage(hipStream_t s, bool debug, const char* stage)
     return HLGS_OK;
 }
 
-enum Stage { ST_PRE = 0, ST_SCAN, ST_RANGES, ST_SCATTER, ST_SORT, ST_BLEND_FWD, ST_BLEND_BWD, ST_GAUSS_BWD,
-             ST_COUNT_TILES, ST_COUNT };
 static const char* kStageNames[ST_COUNT] = {"preprocess", "scan", "tile_ranges", "scatter", "tile_sort",
                                             "blend_fwd", "blend_bwd", "gauss_bwd", "count_tiles"};
 static uint32_t g_timing_mask = 0;  // bit i: time stage i
@@ -322,11 +254,25 @@ size_t hlgs_image_ranges_offset(int W, int H)
 }
 
 namespace hlgs {
-static bool pack_entries_fit(int P) { return P < (1 << (32 - kEntryShift)); }
-static void set_frame_flags(hlgs_frame_info* info, const FrameOpts& o)
+// A frame starts: *info is reset and reports the frame's options.
+static void begin_frame(hlgs_frame_info* info, const FrameOpts& o)
 {
+    info->num_rendered = 0;
+    info->max_tile_count = 0;
+    info->rendered = 0;
+    info->num_binned = 0;
     info->entry_shift = o.pack ? kEntryShift : 0;
     info->drops_empty = o.drop;
+}
+// A frame that blends nothing: colour and inverse depth stay 0 (rasterizer_impl.cu:332-333: not bg).
+static int zero_outputs(const hlgs_raster_args* a, float* out_color, float* out_invdepth, hlgs_frame_info* info,
+                        hipStream_t s)
+{
+    const size_t HW = (size_t)a->W * a->H;
+    HLGS_TRY_HIP(hipMemsetAsync(out_color, 0, 3 * sizeof(float) * HW, s));
+    if (out_invdepth) HLGS_TRY_HIP(hipMemsetAsync(out_invdepth, 0, sizeof(float) * HW, s));
+    info->rendered = 1;
+    return HLGS_OK;
 }
 // Phase 1: preprocess, tile counts, scans, tile ranges (misc = R, longest list, record slots).  With LDS-histogram
 // binning the preprocess also clears tile_count and `seen`, and one k_plan block does both scans and the ranges and
@@ -468,12 +414,8 @@ int hlgs_rasterize_forward_prepare(const hlgs_raster_args* a, void* geom, void* 
 {
     int rc = validate(a);
     if (rc) return rc;
-    info->num_rendered = 0;
-    info->max_tile_count = 0;
-    info->rendered = 0;
-    info->num_binned = 0;
     const FrameOpts o = frame_opts(a->P);  // the frame's options, handed to _render through *info
-    set_frame_flags(info, o);
+    begin_frame(info, o);
     if (a->P == 0) return HLGS_OK;
     hipStream_t s = (hipStream_t)stream;
     if ((rc = prepare_launch(a, o, geom, img, radii, nullptr, nullptr, 0u, s))) return rc;
@@ -519,22 +461,12 @@ int hlgs_rasterize_forward(const hlgs_raster_args* a, void* geom, void* img, int
 {
     int rc = validate(a);
     if (rc) return rc;
-    info->num_rendered = 0;
-    info->max_tile_count = 0;
-    info->rendered = 0;
-    info->num_binned = 0;
     const FrameOpts o = frame_opts(a->P);  // read once: every launch of this frame uses these
-    set_frame_flags(info, o);
+    begin_frame(info, o);
     hipStream_t s = (hipStream_t)stream;
     hipGetLastError();
-    const size_t HW = (size_t)a->W * a->H;
     const bool alt = a->variant == HLGS_VARIANT_ALT;
-    if (a->P == 0) {
-        HLGS_TRY_HIP(hipMemsetAsync(out_color, 0, 3 * sizeof(float) * HW, s));
-        if (out_invdepth) HLGS_TRY_HIP(hipMemsetAsync(out_invdepth, 0, sizeof(float) * HW, s));
-        info->rendered = 1;
-        return HLGS_OK;
-    }
+    if (a->P == 0) return zero_outputs(a, out_color, out_invdepth, info, s);
     Readback* rb;
     if ((rc = readback_for(s, &rb))) return rc;
     if (++rb->seq == 0u) rb->seq = 1u;
@@ -575,12 +507,7 @@ int hlgs_rasterize_forward(const hlgs_raster_args* a, void* geom, void* img, int
     info->num_binned = (int)R;
     info->num_rendered = (int)words[2];
     info->max_tile_count = (int)maxc;
-    if (R == 0 && !alt) {  // rasterizer_impl.cu:332-333: the output stays 0 (not bg)
-        HLGS_TRY_HIP(hipMemsetAsync(out_color, 0, 3 * sizeof(float) * HW, s));
-        if (out_invdepth) HLGS_TRY_HIP(hipMemsetAsync(out_invdepth, 0, sizeof(float) * HW, s));
-        info->rendered = 1;
-        return HLGS_OK;
-    }
+    if (R == 0 && !alt) return zero_outputs(a, out_color, out_invdepth, info, s);
     if (R > (uint32_t)capR) return HLGS_OK;  // caller allocates hlgs_binning_buffer_size(R), calls _render
     if (!spec || maxc > cap_n || replanned) {
         if ((rc = render_launch(a, o, radii, geom, img, binning, capR, maxc, out_color, out_invdepth, seen, s,
@@ -807,16 +734,9 @@ int hlgs_upper_tree_cut_views_device(int N, const int* nodes, const float* xyz, 
                                      float distance_multiplier, int use_frustum, int use_lod, void* scratch, int* cut,
                                      int* count_device, void* stream)
 {
-    if (N < 0) return fail(HLGS_ERR_ARG, "N < 0");
-    if (!count_device) return fail(HLGS_ERR_ARG, "missing count");
-    hipStream_t s = (hipStream_t)stream;
-    if (N == 0) {
-        HLGS_TRY_HIP(hipMemsetAsync(count_device, 0, 2 * sizeof(int), s));
-        return HLGS_OK;
-    }
-    int* dev = nullptr;
-    return upper_cut_launch(N, nodes, xyz, bounds, min_dist2, n_views, planes, campos, distance_multiplier,
-                            use_frustum, use_lod, scratch, cut, count_device, s, &dev);
+    return hlgs_upper_tree_cut_views_ordered_device(N, nodes, nullptr, xyz, bounds, min_dist2, n_views, planes, campos,
+                                                    distance_multiplier, use_frustum, use_lod, scratch, cut,
+                                                    count_device, stream);
 }
 
 int hlgs_upper_tree_cut_views_ordered_device(int N, const int* nodes, const void* order, const float* xyz,
@@ -845,26 +765,25 @@ int hlgs_upper_tree_cut_device(int N, const int* nodes, const float* xyz, const 
                                             use_frustum, use_lod, scratch, cut, count_device, stream);
 }
 
-int hlgs_gather_rows(int64_t n, int row_bytes, const int64_t* idx, const void* src, void* dst, void* stream)
+static int move_rows(bool gather, int64_t n, int row_bytes, const int64_t* idx, const void* src, void* dst, void* stream)
 {
     if (n < 0 || row_bytes < 0 || row_bytes % 4) return fail(HLGS_ERR_ARG, "row size must be a multiple of 4 bytes");
     if (n == 0 || row_bytes == 0) return HLGS_OK;
     if (!idx || !src || !dst) return fail(HLGS_ERR_ARG, "missing tensor");
     hipStream_t s = (hipStream_t)stream;
     hipGetLastError();
-    launch_rows(true, n, row_bytes, idx, src, dst, s);
-    return check_stage(s, false, "gather_rows");
+    launch_rows(gather, n, row_bytes, idx, src, dst, s);
+    return check_stage(s, false, gather ? "gather_rows" : "scatter_rows");
+}
+
+int hlgs_gather_rows(int64_t n, int row_bytes, const int64_t* idx, const void* src, void* dst, void* stream)
+{
+    return move_rows(true, n, row_bytes, idx, src, dst, stream);
 }
 
 int hlgs_scatter_rows(int64_t n, int row_bytes, const int64_t* idx, const void* src, void* dst, void* stream)
 {
-    if (n < 0 || row_bytes < 0 || row_bytes % 4) return fail(HLGS_ERR_ARG, "row size must be a multiple of 4 bytes");
-    if (n == 0 || row_bytes == 0) return HLGS_OK;
-    if (!idx || !src || !dst) return fail(HLGS_ERR_ARG, "missing tensor");
-    hipStream_t s = (hipStream_t)stream;
-    hipGetLastError();
-    launch_rows(false, n, row_bytes, idx, src, dst, s);
-    return check_stage(s, false, "scatter_rows");
+    return move_rows(false, n, row_bytes, idx, src, dst, stream);
 }
 
 size_t hlgs_spt_cache_scratch_size(int n_cut, int m, int R, int num_spts)
@@ -981,26 +900,42 @@ int hlgs_copy_rows(int T, const hlgs_row_copy* tables, int64_t n, const int* src
     return check_stage(s, false, "copy_rows");
 }
 
-int hlgs_copy_rows_packed(int T, const hlgs_row_copy* tables, int64_t n, const int* dev_rows, const int* host_rows,
-                          void* host, int64_t host_row_bytes, int to_host, void* stream)
+// The size checks the two packed row copies share: before the tables are looked at, and per table (a table with
+// rows needs its src and / or dst pointer); words[t] = table t's row length in 32-bit words.
+static int packed_sizes(int T, int64_t n, int64_t host_row_bytes)
 {
     if (T < 0 || T > kMaxRowTables) return fail(HLGS_ERR_ARG, "at most 32 tables");
     if (n < 0) return fail(HLGS_ERR_ARG, "n < 0");
     if (host_row_bytes <= 0 || host_row_bytes % 64 || host_row_bytes > 64 * 4 * kPackSlots)
         return fail(HLGS_ERR_ARG, "host row size must be a multiple of 64 bytes, at most 1024");
-    if (T == 0 || n == 0) return HLGS_OK;
-    if (!tables || !host) return fail(HLGS_ERR_ARG, "missing tables or host storage");
-    float* tabs[kMaxRowTables];
-    int words[kMaxRowTables];
+    return HLGS_OK;
+}
+static int packed_words(int T, const hlgs_row_copy* tables, int64_t host_row_bytes, bool need_src, bool need_dst,
+                        int* words)
+{
     int64_t used = 0;
     for (int t = 0; t < T; t++) {
         if (tables[t].row_bytes < 0 || tables[t].row_bytes % 4) return fail(HLGS_ERR_ARG, "row size must be a multiple of 4 bytes");
-        if (tables[t].row_bytes && !tables[t].src) return fail(HLGS_ERR_ARG, "missing tensor");
-        tabs[t] = (float*)tables[t].src;
+        if (tables[t].row_bytes && ((need_src && !tables[t].src) || (need_dst && !tables[t].dst)))
+            return fail(HLGS_ERR_ARG, "missing tensor");
         words[t] = (int)(tables[t].row_bytes / 4);
         used += tables[t].row_bytes;
     }
     if (used > host_row_bytes) return fail(HLGS_ERR_ARG, "the tables' rows exceed the host row");
+    return HLGS_OK;
+}
+
+int hlgs_copy_rows_packed(int T, const hlgs_row_copy* tables, int64_t n, const int* dev_rows, const int* host_rows,
+                          void* host, int64_t host_row_bytes, int to_host, void* stream)
+{
+    int rc = packed_sizes(T, n, host_row_bytes);
+    if (rc) return rc;
+    if (T == 0 || n == 0) return HLGS_OK;
+    if (!tables || !host) return fail(HLGS_ERR_ARG, "missing tables or host storage");
+    float* tabs[kMaxRowTables];
+    int words[kMaxRowTables];
+    if ((rc = packed_words(T, tables, host_row_bytes, true, false, words))) return rc;
+    for (int t = 0; t < T; t++) tabs[t] = (float*)tables[t].src;
     hipStream_t s = (hipStream_t)stream;
     hipGetLastError();
     launch_rows_packed(T, tabs, words, n, dev_rows, host_rows, (float*)host, (int)(host_row_bytes / 4), to_host != 0, s);
@@ -1010,25 +945,18 @@ int hlgs_copy_rows_packed(int T, const hlgs_row_copy* tables, int64_t n, const i
 int hlgs_load_rows_packed(int T, const hlgs_row_copy* tables, int64_t n, const int* host_rows, const int* resident_of,
                           const void* host, int64_t host_row_bytes, void* stream)
 {
-    if (T < 0 || T > kMaxRowTables) return fail(HLGS_ERR_ARG, "at most 32 tables");
-    if (n < 0) return fail(HLGS_ERR_ARG, "n < 0");
-    if (host_row_bytes <= 0 || host_row_bytes % 64 || host_row_bytes > 64 * 4 * kPackSlots)
-        return fail(HLGS_ERR_ARG, "host row size must be a multiple of 64 bytes, at most 1024");
+    int rc = packed_sizes(T, n, host_row_bytes);
+    if (rc) return rc;
     if (T == 0 || n == 0) return HLGS_OK;
     if (!tables || !host || !host_rows) return fail(HLGS_ERR_ARG, "missing tables, rows or host storage");
     float* dst[kMaxRowTables];
     const float* res[kMaxRowTables];
     int words[kMaxRowTables];
-    int64_t used = 0;
+    if ((rc = packed_words(T, tables, host_row_bytes, resident_of != nullptr, true, words))) return rc;
     for (int t = 0; t < T; t++) {
-        if (tables[t].row_bytes < 0 || tables[t].row_bytes % 4) return fail(HLGS_ERR_ARG, "row size must be a multiple of 4 bytes");
-        if (tables[t].row_bytes && (!tables[t].dst || (resident_of && !tables[t].src))) return fail(HLGS_ERR_ARG, "missing tensor");
         dst[t] = (float*)tables[t].dst;
         res[t] = (const float*)tables[t].src;
-        words[t] = (int)(tables[t].row_bytes / 4);
-        used += tables[t].row_bytes;
     }
-    if (used > host_row_bytes) return fail(HLGS_ERR_ARG, "the tables' rows exceed the host row");
     hipStream_t s = (hipStream_t)stream;
     hipGetLastError();
     launch_rows_packed(T, dst, words, n, nullptr, host_rows, (float*)host, (int)(host_row_bytes / 4), false, s, res,

@@ -57,16 +57,14 @@ struct Geom {
     uint32_t* scan_tmp;
 };
 
-// 64-byte per-Gaussian record read by the blend kernels: one half cache line per (tile, Gaussian)
-// instance instead of one line per attribute array.
+// SplatRec, the layout of Geom::splat: the 64-byte per-Gaussian record read by the blend kernels, one half cache
+// line per (tile, Gaussian) instance instead of one line per attribute array.
 //   [0] x, y, conic.a, conic.b      [1] conic.c, opacity, r, g
 //   [2] b, 1/depth, t, 1/num_kids    [3] unused, first tile x | y << 16, rect width (int bits),
 //                                        alpha threshold on e2 (alpha_e2_threshold)
 // All written by the preprocess.  The Gaussian's record-slot base (the exclusive scan of the rect sizes) is read by
 // the blend backward from point_offsets[idx - 1]: writing it into the record after the scan cost the key scatter a
 // partial-line write per visible Gaussian.
-// lds_binning(P, gx, gy): the LDS-histogram binning plan applies (raster_fwd.hip)
-bool lds_binning(int P, int gx, int gy);
 
 // Tile-list entries (point_list, and the low word of the sort keys) are idx << kEntryShift | quadrant mask whenever
 // the Gaussian count leaves the room (P < 2^28): bit q of the mask says the splat's alpha >= 1/255 footprint reaches
@@ -81,15 +79,12 @@ constexpr int kMiscDrop = 4;  // Img::misc word holding the frame's FrameOpts::d
 constexpr int kMiscFail = 5;  // Img::misc word: a block of the fused plan timed out in its look-back (k_tile_offsets_plan)
 constexpr int kMiscDone = 6;  // Img::misc word: blocks of the fused plan done with their ranges
 constexpr uint32_t kPlanPolls = 1u << 20;  // default bound on each look-back poll of the fused plan (~0.1 s)
+bool pack_entries(int P);
 // drop_empty(P): with packed entries, an instance whose quadrant mask is 0 (its footprint reaches none of the tile's
 // four 8x8 quadrants, so no pixel of the tile blends it) is not binned: the tile lists, the sort and the blends' staging
 // skip it.  Its record slot stays (point_offsets and num_rendered are unchanged) and is never written; k_gauss_bwd
 // skips the slots whose mask is 0 (their records would be zero).  On by default; hlgs_set_drop_empty(0) bins every
 // instance, so point_list and n_contrib are laid out exactly as the reference's binning lays them out.
-// k_plan's words for the host (R, longest list, record slots) in the pinned read-back slot: three 64-bit words, each
-// carrying the frame's sequence number in its high half, written by single-copy-atomic 64-bit stores, so the host
-// waits until all three carry it and the kernel needs no system-scope release (a write-back of the whole L2).
-bool pack_entries(int P);
 bool drop_empty(int P);
 // The frame's binning options, read once from the process-wide test switches (atomics, hlgs_set_entry_packing /
 // hlgs_set_drop_empty / hlgs_set_plan_polls) when the frame starts; nothing inside a frame reads the switches again,
@@ -101,6 +96,8 @@ struct FrameOpts {
     uint32_t flags() const { return (uint32_t)pack | (uint32_t)drop << 1; }  // the plan kernels' flags argument
 };
 FrameOpts frame_opts(int P);
+// lds_binning(P, gx, gy): the LDS-histogram binning plan applies (raster_fwd.hip)
+bool lds_binning(int P, int gx, int gy);
 // Does the forward's preprocess (k_preprocess_sh2) leave Geom::sh_jac for the SH backward?  Same condition as its launch.
 inline bool sh_jac_written(const hlgs_raster_args& a)
 {
@@ -171,6 +168,41 @@ __device__ __forceinline__ bool guard_fail(const Guard& gd)
     return gd.misc && (gd.misc[0] > gd.cap_R || gd.misc[1] > gd.cap_n);
 }
 
+// Rasterizer stages, in hlgs_stage_name order; stage_mark (capi.hip) times a stage when hlgs_set_stage_timing asks.
+enum Stage { ST_PRE = 0, ST_SCAN, ST_RANGES, ST_SCATTER, ST_SORT, ST_BLEND_FWD, ST_BLEND_BWD, ST_GAUSS_BWD,
+             ST_COUNT_TILES, ST_COUNT };
+void stage_mark(hipStream_t s, int stage, bool begin);
+
+// preprocess.hip
+void launch_preprocess(const hlgs_raster_args& a, const Geom& g, int* radii, uint32_t* tile_count, int gx, int gy,
+                       const ZeroJob& z, hipStream_t s);
+// raster_fwd.hip
+uint32_t* bin_histogram(const Img& im, int P, int gx, int gy);
+void launch_count_tiles(int P, const int* radii, const Geom& g, const Img& im, int gx, int gy, bool alt,
+                        hipStream_t s, uint32_t* hist, bool fused);
+// k_plan's words for the host (R, longest list, record slots) in the pinned read-back slot `host`: three 64-bit
+// words, each carrying the frame's sequence number in its high half, written by single-copy-atomic 64-bit stores, so
+// the host waits until all three carry it and the kernel needs no system-scope release (a write-back of the whole L2).
+void launch_plan(int P, const Geom& g, const Img& im, int gx, int gy, uint32_t* host, uint32_t seq, hipStream_t s,
+                 bool fused);
+void launch_tile_ranges(const Img& im, int T, const uint32_t* point_offsets, int P, uint32_t flags, hipStream_t s);
+void launch_binning(const hlgs_raster_args& a, const int* radii, const Geom& g, const Img& im, const Bin& b, int gx,
+                    int gy, uint32_t max_count, hipStream_t s, bool timing, Guard gd);
+void launch_blend_fwd(const hlgs_raster_args& a, const Geom& g, const Img& im, const Bin& b, int gx, int gy,
+                      float* out_color, float* out_invdepth, int* seen, hipStream_t s, Guard gd);
+void launch_mark_visible(int P, const float* means, const float* view, uint8_t* present, hipStream_t s);
+void launch_relocation(int P, const float* oo, const float* so, const int* N, const float* binoms, int n_max,
+                       float* on, float* sn, hipStream_t s);
+// raster_bwd.hip
+void launch_blend_bwd(const hlgs_raster_args& a, const Geom& g, const Img& im, const Bin& b, const BwdScratch& rs,
+                      int gx, int gy, const float* dL_dpix, const float* dL_dinv, hipStream_t s);
+// gauss_bwd.hip
+void launch_gauss_bwd(const hlgs_raster_args& a, const int* radii, const Geom& g, const BwdScratch& rs,
+                      const hlgs_grads& o, bool has_depth, hipStream_t s, hipStream_t late, hipEvent_t ev,
+                      const uint32_t* misc);
+void launch_sh_from_colour(int P, int V, int D, int M, bool alt, const float* means, const float* campos,
+                           const float* drgb, int64_t stride, float scale, float* dsh, float* ddc, hipStream_t s);
+
 // Upper-tree cut (stream.hip).  Per level the frontier (the reference's `stack`) is filtered by the cull;
 // leaves go to the cut, then the non-leaves whose LOD condition is false, each group in frontier order; the
 // next frontier is the first children of the expanded nodes in order, then their first children's next
@@ -207,6 +239,8 @@ struct CutArgs {
     CutFlat* flat;
 };
 size_t upper_cut_state_bytes();
+void launch_upper_cut(const CutArgs& a, hipStream_t s);
+void launch_upper_cut_flat(const CutArgs& a, const int* order, hipStream_t s);
 
 // SPT cache bookkeeping of one streaming step (stream.hip, train_post.py:346-430)
 struct CacheArgs {
@@ -244,6 +278,7 @@ void launch_cache_lists(const CacheArgs& a, hipStream_t s);
 void launch_cache_keep(int R, int sky, const uint32_t* diff_incl, uint32_t* keep, hipStream_t s);
 void launch_cache_split(int R, const int* render, const uint32_t* keep_incl, int* keep_rows, int* render_kept,
                         int* wb_rows, int* wb_indices, hipStream_t s);
+void launch_rows(bool gather, long n, int row_bytes, const int64_t* idx, const void* src, void* dst, hipStream_t s);
 struct RowCopy {
     const void* src;
     void* dst;
@@ -269,11 +304,54 @@ struct AdamTensor {
 };
 void launch_adam_multi(int T, const AdamTensor* t, int sky, float b1, float a1, float b2, float a2, float bc2_sqrt,
                        float eps, hipStream_t s);
+void launch_adam(float* param, const float* grad, float* m, float* v, const uint8_t* vis, float lr, float b1, float b2,
+                 float eps, uint32_t N, uint32_t M, hipStream_t s);
+
+// act.hip
+void launch_act_fwd(int64_t n, const float* op_raw, const float* sc_raw, const float* rot_raw, float* op, float* sc,
+                    float* rot, hipStream_t s);
+void launch_act_bwd(int64_t n, const float* op, const float* sc, const float* rot_raw, const float* g_op,
+                    const float* g_sc, const float* g_rot, float* d_op, float* d_sc, float* d_rot, hipStream_t s);
+
+// loss.hip
+size_t ssim_partials(int C, int H, int W);
+void launch_ssim_forward(int C, int H, int W, const float* img1, const float* img2, int valid, float* abc,
+                         float* partial, float* out, hipStream_t s, bool clamp1);
+void launch_ssim_backward(int C, int H, int W, const float* img1, const float* img2, const float* abc,
+                          const float* coef, float* grad1, hipStream_t s, bool clamp1);
+int depth_l1_blocks(long n);
+void launch_depth_l1_forward(long n, const float* inv, const float* mono, const float* mask, float* partial,
+                             float* out, hipStream_t s);
+void launch_depth_l1_backward(long n, const float* inv, const float* mono, const float* mask, const float* coef,
+                              float* grad, hipStream_t s);
+
+// lod.hip
+void launch_morton(int P, const float* xyz, const float* mn, const float* mx, int64_t* codes, hipStream_t s);
+void launch_expand_dynamic(int N, float target, const int* nodes, const float* pos, const float* scales,
+                           const float* vp, const float* vd, int* ri, int* pi, int* ni, uint32_t* counts,
+                           uint32_t* incl, uint32_t* tmp, hipStream_t s);
+void launch_weights_dynamic(int n, const int* idx, float target, const int* nodes, const float* pos,
+                            const float* scales, const float* vp, float* ts, int* kids, hipStream_t s);
+void launch_expand_static(int N, float target, const int* nodes, const float* boxes, const float* vp, int* ri,
+                          int* pi, int* ni, uint32_t* counts, uint32_t* incl, uint32_t* tmp, hipStream_t s);
+void launch_weights_static(int n, const int* idx, float target, const int* nodes, const float* boxes,
+                           const float* vp, float* ts, int* kids, hipStream_t s);
+void launch_spt_prepare(int s_, const int* starts, const float* smax, const int* sidx, const float* sdist,
+                        uint32_t* sizes, uint32_t* incl, uint32_t* tmp, hipStream_t s);
+void launch_spt_finish(int s_, int E, int n, const int* gidx, const int* starts, const float* smin, const int* sidx,
+                       const float* sdist, int compat, const uint32_t* sizes, const uint32_t* incl, uint32_t* counts,
+                       uint32_t* counts_incl, uint32_t* tmp_s, int* result, uint32_t* keep, uint32_t* keep_incl,
+                       uint32_t* tmp_n, int* cut, int* counts_prefix, hipStream_t s);
+void launch_lod_interp_fwd(int S, int n, int M3, const int* ridx, const int* pidx, const float* w, const float* means,
+                           const float* scales, const float* rots, const float* opac, const float* shs, float* om,
+                           float* osc, float* orot, float* oop, float* osh, hipStream_t s);
+size_t lerp_bwd_scratch_elems(int P, int n);
+void launch_lod_interp_bwd(int P, int S, int n, int M3, const int* ridx, const int* pidx, const float* w,
+                           const float* rots, const float* gm, const float* gsc, const float* grot, const float* gop,
+                           const float* gsh, float* dm, float* dsc, float* drot, float* dop, float* dsh, void* scratch,
+                           hipStream_t s);
 
 // scan.hip
 void scan_inclusive_u32(const uint32_t* in, uint32_t* out, size_t n, uint32_t* tmp, hipStream_t s);
-
-// stage timing (capi.cpp)
-void stage_mark(hipStream_t s, int stage, bool begin);
 
 }  // namespace hlgs

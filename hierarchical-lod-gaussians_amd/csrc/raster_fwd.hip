@@ -1423,7 +1423,7 @@ void launch_binning(const hlgs_raster_args& a, const int* radii, const Geom& g, 
 {
     const int T = gx * gy;
     const int alt = a.variant == HLGS_VARIANT_ALT;
-    if (timing) stage_mark(s, 3, true);
+    if (timing) stage_mark(s, ST_SCATTER, true);
     if (lds_binning(a.P, gx, gy)) {
         allow_big_lds();
 #define HLGS_SCATTER(BG, PK)                                                                                       \
@@ -1437,7 +1437,7 @@ void launch_binning(const hlgs_raster_args& a, const int* radii, const Geom& g, 
     } else
         hipLaunchKernelGGL(k_scatter_keys, dim3((a.P + 255) / 256), dim3(256), 0, s, a.P, radii, g, im.ranges,
                            im.tile_cursor, b.keys, gx, gy, alt, gd, g.pack);
-    if (timing) { stage_mark(s, 3, false); stage_mark(s, 4, true); }
+    if (timing) { stage_mark(s, ST_SCATTER, false); stage_mark(s, ST_SORT, true); }
     const KeySrc ks{reinterpret_cast<const uint32_t*>(b.keys), g.depths, g.pack};
     hipLaunchKernelGGL(k_tile_sort_wave, dim3(T), dim3(64), 0, s, im.ranges, ks, b.point_list, T, gd);
     if (max_count > (uint32_t)kWaveSortCap)
@@ -1452,7 +1452,7 @@ void launch_binning(const hlgs_raster_args& a, const int* radii, const Geom& g, 
             uint64_t* t = src; src = dst; dst = t;
         }
     }
-    if (timing) stage_mark(s, 4, false);
+    if (timing) stage_mark(s, ST_SORT, false);
 }
 
 void launch_blend_fwd(const hlgs_raster_args& a, const Geom& g, const Img& im, const Bin& b, int gx, int gy,

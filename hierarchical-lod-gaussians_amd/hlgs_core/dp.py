@@ -40,7 +40,7 @@ def _drop_entries(keys, token):
 def direct_grad(t, late=False):
     """Destination for the gradient of input tensor `t`, or None.
 
-    Used by the rasterizer backward (diff_gaussian_rasterization._C, alt_gaussian_rasterization._C): when `t` is a
+    Used by the rasterizer backward (hlgs_core.raster, for both front ends): when `t` is a
     parameter registered by a FlatGradExchange(direct=True) and its .grad is unset, the backward writes the
     gradient into the exchange's flat buffer, autograd adopts that tensor as .grad (it steals a fresh leaf
     gradient instead of copying it), and the all-reduce finds it already packed.  With .grad set (accumulation)

@@ -84,6 +84,8 @@ def test_public_signatures_match_reference():
                                           "rotations", "cov3Ds_precomp", "raster_settings"]
     assert sig(D.compute_relocation) == ["opacity_old", "scale_old", "N", "binoms", "n_max"]
     assert len(sig(D._C.rasterize_gaussians)) == 24 and len(sig(D._C.rasterize_gaussians_backward)) == 27
+    import alt_gaussian_rasterization as A
+    assert len(sig(A._C.rasterize_gaussians)) == 21 and len(sig(A._C.rasterize_gaussians_backward)) == 27
     assert sig(G.expand_to_size_dynamic)[:9] == ["nodes", "positions", "scales", "size", "viewpoint", "viewdir",
                                                  "render_indices", "parent_indices", "nodes_for_render_indices"]
     assert sig(G.get_interpolation_weights_dynamic) == ["indices", "size", "nodes", "positions", "scales",
@@ -117,6 +119,55 @@ def test_no_cpu_fallback():
     with pytest.raises(RuntimeError, match="means3D must have dimensions"):
         _C.rasterize_gaussians(torch.zeros(3), e, e, e, e, torch.zeros(4, 2), e, e, e, e, 1.0, e, torch.eye(4),
                                torch.eye(4), 0.5, 0.5, 16, 16, e, 0, torch.zeros(3), False, False, True)
+
+
+def _alt_forward(means3D, n):
+    from alt_gaussian_rasterization import _C
+    e = torch.empty(0)
+    return _C.rasterize_gaussians(torch.zeros(3), means3D, e, torch.zeros(n, 1), torch.ones(n, 3), torch.ones(n, 4),
+                                  1.0, e, torch.eye(4), torch.eye(4), 0.5, 0.5, 12, 16, torch.zeros(n, 1, 3),
+                                  torch.zeros(n, 0, 3), 0, torch.zeros(3), False, True, False)
+
+
+def test_no_cpu_fallback_alt():
+    """The alt front end raises as the hierarchy one does: the shape error first, then the missing device."""
+    if torch.cuda.is_available():
+        pytest.skip("GPU present")
+    with pytest.raises(RuntimeError, match="HIP device"):
+        _alt_forward(torch.zeros(4, 3), 4)
+    with pytest.raises(RuntimeError, match="means3D must have dimensions"):
+        _alt_forward(torch.zeros(4, 2), 4)
+
+
+def test_alt_without_gaussians_launches_nothing():
+    """P == 0 (rasterize_points.cu:88-90): forward returns zero images and empty buffers, backward its nine empty
+    gradients; neither needs a device."""
+    from alt_gaussian_rasterization import _C
+    out = _alt_forward(torch.zeros(0, 3), 0)
+    assert len(out) == 9 and out[0] == 0 and out[1] == 0
+    assert out[2].shape == (3, 12, 16) and out[3].shape == (1, 12, 16)
+    assert not out[2].any() and not out[3].any()
+    assert out[4].shape == (0,) and out[4].dtype == torch.int32
+    assert all(b.shape == (0,) and b.dtype == torch.uint8 for b in out[5:])
+    e = torch.empty(0)
+    z = lambda *s: torch.zeros(0, *s)  # noqa: E731
+    grads = _C.rasterize_gaussians_backward(torch.zeros(3), z(3), out[4], e, z(1), z(3), z(4), 1.0, e, torch.eye(4),
+                                            torch.eye(4), 0.5, 0.5, torch.zeros(3, 12, 16), z(1, 3), z(15, 3),
+                                            torch.zeros(1, 12, 16), 3, torch.zeros(3), out[5], out[0], out[6], out[7],
+                                            out[1], out[8], True, False)
+    # an sh without rows counts as no sh (rasterize_points.cu:97-101), so M = 0 in dL_dsh
+    assert [tuple(t.shape) for t in grads] == [(0, 3), (0, 3), (0, 1), (0, 3), (0, 6), (0, 1, 3), (0, 0, 3), (0, 3),
+                                               (0, 4)]
+
+
+def test_front_ends_share_one_binding():
+    import alt_gaussian_rasterization as A
+    import diff_gaussian_rasterization as D
+    from hlgs_core import raster
+    assert A._C.mark_visible is D._C.mark_visible is raster.mark_visible
+    assert A._C.compute_relocation is D._C.compute_relocation is raster.compute_relocation
+    # the binning hints stay per front end
+    assert A._C._binning_hint is not D._C._binning_hint
 
 
 def test_product_sources_have_no_variant_switches():

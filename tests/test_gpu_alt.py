@@ -186,6 +186,25 @@ def test_alt_backward_is_deterministic():
             np.testing.assert_array_equal(a[k], b[k])
 
 
+def test_alt_binning_capacity_fallback_matches():
+    """One-call forward with a too-small cached binning buffer (second call path), an exact one and an
+    oversized one all give the same frame and the same backward, through the alt front end's own hint."""
+    from alt_gaussian_rasterization import _C
+    sc, cam = _alt_scene(2500, 2, 160, 120, seed=21)
+    g = S.upstream_grads(160, 120, seed=1)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    runs = []
+    try:
+        for hint in (1, 0, 1 << 26):
+            _C._binning_hint[dev] = hint
+            runs.append(_gpu(sc, cam, g))
+    finally:
+        _C._binning_hint.pop(dev, None)
+    for r in runs[1:]:
+        for k in ("color", "invdepth", "radii", "dmean3D", "dmean2D", "dopacity", "dscale", "drot", "ddc", "dshs"):
+            np.testing.assert_array_equal(runs[0][k], r[k])
+
+
 def _adam_ref(p, g, m, v, vis, lr, b1, b2, eps, M):
     p, m, v = p.copy(), m.copy(), v.copy()
     on = np.repeat(vis, M)[: p.size]
