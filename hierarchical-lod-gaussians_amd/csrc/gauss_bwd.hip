@@ -668,7 +668,8 @@ __global__ void __launch_bounds__(128) k_sh_bwd_jac2(hlgs_raster_args a, const i
         for (int f = threadIdx.x; f < n * Q; f += 128) {
             const int r = f / Q, q = f - r * Q;
             const float* lp = s_rows + r * kShStride + 4 * q;
-            reinterpret_cast<float4*>(gbase)[f] = make_float4(lp[0], lp[1], lp[2], lp[3]);
+            // non-temporal: the gradient rows are next read by the caller's optimizer, after the rest of the backward
+            store_nt(reinterpret_cast<float4*>(gbase) + f, make_float4(lp[0], lp[1], lp[2], lp[3]));
         }
     } else {
         for (int f = threadIdx.x; f < n * M3; f += 128) {

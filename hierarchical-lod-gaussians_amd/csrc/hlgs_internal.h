@@ -157,6 +157,22 @@ __device__ __forceinline__ void zero_prelude(const ZeroJob& z, int tid, int nthr
         for (int i = tid; i < z.T; i += nthreads) z.tile_count[i] = 0;
 }
 
+// Non-temporal float4 accesses for streams that pass once and are next touched, if at all, after far more traffic
+// than the caches hold: the SH rows the preprocess reads, the direction Jacobians it writes for the backward and the
+// SH gradient rows the backward writes.  They do not displace the lines the next kernels read again (the records,
+// the tile lists) from L2 and the memory-side cache.
+typedef float nt_f4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ float4 load_nt(const float4* p)
+{
+    const nt_f4 v = __builtin_nontemporal_load(reinterpret_cast<const nt_f4*>(p));
+    return make_float4(v.x, v.y, v.z, v.w);
+}
+__device__ __forceinline__ void store_nt(float4* p, const float4& a)
+{
+    const nt_f4 v = {a.x, a.y, a.z, a.w};
+    __builtin_nontemporal_store(v, reinterpret_cast<nt_f4*>(p));
+}
+
 // Speculative render (hlgs_rasterize_forward): the render kernels are queued before the host has read
 // R and the longest tile list; each exits at once when they exceed what the launch was sized for.
 struct Guard {

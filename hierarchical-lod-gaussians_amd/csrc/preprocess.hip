@@ -275,7 +275,10 @@ __device__ __forceinline__ bool preprocess_geom(const hlgs_raster_args& a, const
 // waves busy.  Same arithmetic, same outputs.
 // The rows arrive through registers: every lane loads consecutive float4s of the block's contiguous rows (1 KiB per
 // wave instruction) and stores them into LDS rows of odd stride (kShStride), so that each lane's own row walk hits
-// distinct banks; degree-3 rows use the unpadded swizzled float4 layout of sh_rows_load_swz below instead.  (Round 5 measured LDS-DMA into a chunk-major image instead -- conflict-free b128 reads, no staging
+// distinct banks; degree-3 rows use the unpadded swizzled float4 layout of sh_rows_load_swz below instead.  The float4
+// row loads and the Jacobian stores are non-temporal (load_nt / store_nt, hlgs_internal.h): the rows are read once per
+// frame and the Jacobians are next read by the backward, so neither should take cache lines from the records this
+// kernel writes for the binning kernels and the blend (90 -> 66 us at 1M Gaussians).  (Round 5 measured LDS-DMA into a chunk-major image instead -- conflict-free b128 reads, no staging
 // registers: 115 against 97 us, because the DMA's source side then reads 16 bytes per lane at the row stride, 64 lines
 // per wave instruction instead of 8; preprocess_dma.hip, tools/variants/INDEX.md.)
 template <int M3T>
@@ -287,7 +290,7 @@ __device__ __forceinline__ void sh_rows_load_contig(const float* gbase, float* l
 #pragma unroll
         for (int k = 0; k < Q; k++) {
             const int f = lane + 64 * k;
-            v[k] = f < n * Q ? reinterpret_cast<const float4*>(gbase)[f] : make_float4(0.f, 0.f, 0.f, 0.f);
+            v[k] = f < n * Q ? load_nt(reinterpret_cast<const float4*>(gbase) + f) : make_float4(0.f, 0.f, 0.f, 0.f);
         }
 #pragma unroll
         for (int k = 0; k < Q; k++) {
@@ -318,7 +321,7 @@ __device__ __forceinline__ void sh_rows_load_swz(const float* gbase, float* lds,
 #pragma unroll
     for (int k = 0; k < 12; k++) {
         const int f = lane + 64 * k;
-        v[k] = f < n * 12 ? reinterpret_cast<const float4*>(gbase)[f] : make_float4(0.f, 0.f, 0.f, 0.f);
+        v[k] = f < n * 12 ? load_nt(reinterpret_cast<const float4*>(gbase) + f) : make_float4(0.f, 0.f, 0.f, 0.f);
     }
 #pragma unroll
     for (int k = 0; k < 12; k++) {
@@ -421,7 +424,11 @@ __global__ void __launch_bounds__(128) k_preprocess_sh2(hlgs_raster_args a, Geom
             float* jb = g.sh_jac + 9 * (size_t)t0;  // 16-byte aligned: t0 is a multiple of 64
             for (int f4 = lane; 4 * f4 < nf; f4 += 64) {
                 if (4 * f4 + 3 < nf) {
-                    reinterpret_cast<float4*>(jb)[f4] = reinterpret_cast<const float4*>(s_jac)[f4];
+                    // non-temporal with the float4 row loads (the wide rows); the narrow rows' kernels are unchanged
+                    if constexpr (M3T > 0 && M3T % 4 == 0)
+                        store_nt(reinterpret_cast<float4*>(jb) + f4, reinterpret_cast<const float4*>(s_jac)[f4]);
+                    else
+                        reinterpret_cast<float4*>(jb)[f4] = reinterpret_cast<const float4*>(s_jac)[f4];
                 } else {
                     for (int e = 4 * f4; e < nf; e++) jb[e] = s_jac[e];
                 }
