@@ -496,7 +496,10 @@ void hlgs_set_drop_empty(int on);
 void hlgs_set_plan_polls(unsigned polls);
 size_t hlgs_image_ranges_offset(int W, int H);  /* uint2 ranges[tiles] */
 /* uint32 misc[16]: [0] binned instances, [1] longest tile list, [2] record slots, [3] the frame's entry packing (1 when
- * entry_shift != 0), [4] the frame's drops_empty -- written on the device by the frame's binning plan */
+ * entry_shift != 0), [4] the frame's drops_empty -- written on the device by the frame's binning plan; [5] non-zero when
+ * a look-back of the frame's fused plan timed out (hlgs_set_plan_polls) and the frame was planned again by the
+ * two-launch plan, which leaves the word set: the count kernel of the next fused plan clears it (LDS-histogram binning
+ * only; the other words are not defined) */
 size_t hlgs_image_misc_offset(int W, int H);
 size_t hlgs_geom_splat_offset(int P);           /* float4 splat[P][4]: x, y, conic a, b | conic c, opacity, r, g |
                                                    b, 1/depth, t, 1/kids | record base, tile x0, y0, width */

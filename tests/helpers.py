@@ -107,6 +107,76 @@ def oracle_render(scene, cam, do_depth=True, grads=None, use_colors=False, use_c
     return out
 
 
+def bin_gauss(P):
+    """Gaussians per binning block of a P-Gaussian frame (csrc/raster_fwd.hip bin_gauss), restated for the tests that
+    sit on its threshold and on those of nb = ceil(P / bin_gauss(P))."""
+    return 4096 if P > 768 * 1024 else 1024
+
+
+def one_tile_scene(n, seed, deg=0, opacity=(0.02, 0.06), alt=False, aa=True):
+    """-> (scene, cam): n faint isotropic splats (sigma = 1 px, radius 4) whose centres project into the middle
+    7 x 7 pixels of tile (1, 1) of a 64 x 64 frame, so that every footprint stays inside that tile: exactly one
+    non-empty tile, whose list holds exactly n entries (tests/test_dispatch_scenes_cpu.py asserts it from the oracle).
+    The list length is what selects the tile sort, the backward's chunking and the blends' batch count.
+    alt: the scene in the alt rasterizer's layout (dc / shs split, as test_gpu_alt._alt_scene)."""
+    W = H = 64
+    cam = S.make_camera(W, H)
+    sc = S.make_gaussians(n, deg, cam, seed, zmin=4, zmax=8)
+    rng = np.random.Generator(np.random.PCG64(seed + 1000))
+    z = sc["means3D"][:, 2].astype(np.float64)
+    px = rng.uniform(16 + 4.5, 16 + 11.5, n)
+    py = rng.uniform(16 + 4.5, 16 + 11.5, n)
+    sc["means3D"][:, 0] = (((2 * px + 1) / W - 1) * cam["tanfovx"] * z).astype(np.float32)
+    sc["means3D"][:, 1] = (((2 * py + 1) / H - 1) * cam["tanfovy"] * z).astype(np.float32)
+    sc["scales"] = np.ascontiguousarray(np.repeat((1.0 * z / cam["fx"])[:, None], 3, 1).astype(np.float32))
+    sc["opacities"] = rng.uniform(opacity[0], opacity[1], (n, 1)).astype(np.float32)
+    if alt:
+        sc["dc"] = np.ascontiguousarray(sc["shs"][:, :1])
+        sc["shs"] = np.ascontiguousarray(sc["shs"][:, 1:])
+        sc["alt"] = True
+        sc["antialiasing"] = aa
+    return sc, cam
+
+
+def equal_depths(sc, z=6.0):
+    """Move every Gaussian of a camera-at-origin scene (one_tile_scene) along its view ray to depth z, scaled with it,
+    so that the projected centres and sizes stay and every sort key ties: the lists must then come out in index
+    order.  In place; returns sc."""
+    k = (z / sc["means3D"][:, 2].astype(np.float64))[:, None]
+    sc["means3D"] = np.ascontiguousarray((sc["means3D"] * k).astype(np.float32))
+    sc["means3D"][:, 2] = np.float32(z)
+    sc["scales"] = np.ascontiguousarray((sc["scales"] * k).astype(np.float32))
+    return sc
+
+
+def sparse_scene(P, seed, W, H, deg, visible=4000):
+    """-> (scene, cam, shown): P Gaussians of which only `visible` random ones (shown, sorted indices) can reach the
+    frame; the others are hidden by thirds -- behind the camera (z negated), far outside the frustum (x += 40 z) or
+    inside the near cull (z = 0.1).  The frame's cost is that of a few thousand Gaussians while P, which selects the
+    binning block size and the plan kernels' code paths, is as large as the threshold needs; the visible ones are
+    spread over the count blocks, so every histogram row matters.  The last Gaussian is always shown and put on the
+    optical axis: one Gaussian past a multiple of the block size, it is the whole last count block."""
+    cam = S.make_camera(W, H)
+    sc = S.make_gaussians(P, deg, cam, seed)
+    rng = np.random.Generator(np.random.PCG64(seed + 2000))
+    shown = np.union1d(rng.choice(P, min(visible, P), replace=False), [P - 1])
+    hide = np.ones(P, bool)
+    hide[shown] = False
+    idx = np.nonzero(hide)[0]
+    m = sc["means3D"]
+    a, b, c = idx[0::3], idx[1::3], idx[2::3]
+    m[a, 2] = -m[a, 2]
+    m[b, 0] += 40 * m[b, 2]
+    m[c, 2] = 0.1
+    m[P - 1] = (0.0, 0.0, 5.0)
+    return sc, cam, shown
+
+
+def tile_counts(fr):
+    """Per-tile list lengths of an oracle frame."""
+    return fr.ranges[:, 1].astype(np.int64) - fr.ranges[:, 0].astype(np.int64)
+
+
 def rel_err(a, b):
     """max |a-b| / max |b| (per tensor) -- the 1e-3 gradient criterion of BASELINE.json north_star."""
     a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
