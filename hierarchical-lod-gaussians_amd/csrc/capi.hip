@@ -674,6 +674,21 @@ int hlgs_morton_codes(int P, const float* xyz, const float* mn, const float* mx,
     return check_stage(s, false, "morton_codes");
 }
 
+// ---------------------------------------------------------------- 3-nearest-neighbour distances (knn.hip)
+size_t hlgs_knn_scratch_size(int P) { return knn_scratch_bytes(P); }
+
+int hlgs_knn_mean_dist2(int P, const float* xyz, void* scratch, float* out, void* stream)
+{
+    if (P < 0) return fail(HLGS_ERR_ARG, "P < 0");
+    if (P == 0) return HLGS_OK;
+    if (!xyz || !scratch || !out) return fail(HLGS_ERR_ARG, "missing tensor");
+    if ((uintptr_t)scratch % 16) return fail(HLGS_ERR_ARG, "scratch must be 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    hipGetLastError();
+    launch_knn(P, xyz, scratch, out, s);
+    return check_stage(s, false, "knn");
+}
+
 // ---------------------------------------------------------------- SPT streaming (stream.hip)
 size_t hlgs_upper_cut_scratch_size(int N)
 {

@@ -367,6 +367,17 @@ void launch_lod_interp_bwd(int P, int S, int n, int M3, const int* ridx, const i
                            const float* gsh, float* dm, float* dsc, float* drot, float* dop, float* dsh, void* scratch,
                            hipStream_t s);
 
+// knn.hip: 3-nearest-neighbour mean squared distance.  A box is kKnnBox consecutive Morton-sorted points (one wave of
+// the search), a super-box kKnnSuper consecutive boxes (one lane each in the box test), a sort tile the kKnnSortTile
+// keys one block of a radix pass histograms and scatters.
+constexpr int kKnnBox = HLGS_KNN_BOX;
+constexpr int kKnnSuper = HLGS_KNN_SUPER;
+constexpr int kKnnSortTile = HLGS_KNN_SORT_TILE;
+static_assert(kKnnBox == 64 && kKnnSuper == 64, "one lane per row of a box and per box of a super-box");
+static_assert(kKnnSortTile % 256 == 0, "a sort tile is whole rounds of the histogram's 256 threads");
+size_t knn_scratch_bytes(int P);
+void launch_knn(int P, const float* xyz, void* scratch, float* out, hipStream_t s);
+
 // scan.hip
 void scan_inclusive_u32(const uint32_t* in, uint32_t* out, size_t n, uint32_t* tmp, hipStream_t s);
 

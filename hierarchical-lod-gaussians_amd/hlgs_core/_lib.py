@@ -91,6 +91,8 @@ _SIGS = {
     "hlgs_compute_relocation": (_i, [_i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
     "hlgs_adam_update": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, C.c_uint32, C.c_uint32, _vp]),
     "hlgs_morton_codes": (_i, [_i, _vp, _vp, _vp, _vp, _vp]),
+    "hlgs_knn_scratch_size": (_sz, [_i]),
+    "hlgs_knn_mean_dist2": (_i, [_i, _vp, _vp, _vp, _vp]),
     "hlgs_upper_cut_scratch_size": (_sz, [_i]),
     "hlgs_upper_tree_cut": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _i, _vp, _vp, C.POINTER(_i), _vp]),
     "hlgs_upper_tree_cut_device": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _i, _vp, _vp, _vp, _vp]),

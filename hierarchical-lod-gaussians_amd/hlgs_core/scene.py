@@ -1,5 +1,6 @@
 """Scene assembly around a loaded dynamic hierarchy: the tensor bookkeeping of GaussianModel.create_from_hier
-(scene/gaussian_model.py:990-1095) and sort_morton (:570-589), without the training state around them.
+(scene/gaussian_model.py:990-1095) and sort_morton (:570-589), without the training state around them, and the
+initial scales create_from_pcd gives the Gaussians of a point cloud (:848-852).
 
 assemble_hierarchy() takes what gaussian_hierarchy.load_dynamic_hierarchy returns plus an optional scaffold
 (skybox) point set and produces the model tensors the renderers read: skybox rows prepended, node indices
@@ -56,3 +57,16 @@ def morton_order(xyz, skybox_points=0):
     indices[root_index] = indices[0]
     indices[0] = 0
     return indices + skybox_points
+
+
+def initial_log_scales(xyz, skybox_points=0, scaffold=False):
+    """The initial log-scales of create_from_pcd (gaussian_model.py:848-852) for the (P, 3) device positions `xyz`,
+    whose first skybox_points rows are the skybox shell: the mean squared distance to the three nearest other points
+    (simple_knn.distCUDA2), at least 1e-7; without a scaffold file the skybox rows are scaled by 10 and the others
+    capped at 10; then log(sqrt(.)) in all three columns.  Returns (P, 3) float32."""
+    from simple_knn._C import distCUDA2
+    dist2 = torch.clamp_min(distCUDA2(xyz), 0.0000001)
+    if not scaffold and skybox_points > 0:
+        dist2[:skybox_points] *= 10
+        dist2[skybox_points:] = torch.clamp_max(dist2[skybox_points:], 10)
+    return torch.log(torch.sqrt(dist2))[..., None].repeat(1, 3)

@@ -248,6 +248,24 @@ int hlgs_lod_interp_backward(int P, int S, int n, int M3, const int* ridx, const
  * scene/gaussian_model.py:570-589). */
 int hlgs_morton_codes(int P, const float* xyz, const float* mn, const float* mx, int64_t* codes, void* stream);
 
+/* Mean squared distance to the three nearest other points: simple_knn._C.distCUDA2, imported by
+ * scene/gaussian_model.py:21 and used at :848 (create_from_pcd), where the initial scale of every Gaussian is
+ * log(sqrt(clamp_min(distCUDA2(xyz), 1e-7))).  xyz: P x 3 device floats; out: P device floats.  For each point i the
+ * squared distances d(i, j) = (dx*dx + dy*dy) + dz*dz to all other indices j are taken in float32, every operation
+ * rounded on its own (no fma, no |a|^2 + |b|^2 - 2 a.b form); with b0 <= b1 <= b2 the three smallest,
+ * out[i] = ((b0 + b1) + b2) / 3.0f.  Coincident points are ordinary neighbours at distance 0.  A missing neighbour
+ * (P < 4) counts as +inf, so every output is +inf then.  The result equals the all-pairs scan bit for bit and does not
+ * change from run to run.  P == 0 launches nothing.  No host synchronisation; every memory index stays in range for
+ * any input bits (outputs of rows with non-finite coordinates are unspecified).
+ * scratch: hlgs_knn_scratch_size(P) bytes of device memory, 16-byte aligned.
+ * The search works on boxes of HLGS_KNN_BOX Morton-sorted points grouped into super-boxes of HLGS_KNN_SUPER boxes;
+ * the radix sort handles HLGS_KNN_SORT_TILE keys per block. */
+#define HLGS_KNN_BOX 64
+#define HLGS_KNN_SUPER 64
+#define HLGS_KNN_SORT_TILE 1024
+size_t hlgs_knn_scratch_size(int P);
+int hlgs_knn_mean_dist2(int P, const float* xyz, void* scratch, float* out, void* stream);
+
 /* ---- SPT streaming around the SPT cut (train_post.py:323-491) ---- */
 /* Coarse cut of the upper tree (GaussianModel.cut_hierarchy_on_condition with root 0, no upper-tree output,
  * leave_out_of_cut_condition = frustum_cull_spheres: scene/gaussian_model.py:364-404, 67-100, as train_post.py

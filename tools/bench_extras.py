@@ -9,6 +9,9 @@
   loss      photometric_loss (L1 + D-SSIM + masked inverse-depth L1) forward + backward on a 1080p view.
   adam      SparseGaussianAdam.step over 1M Gaussians (59 floats each, six parameter groups), half visible.
   morton    get_morton_indices over the hierarchy's nodes.
+  knn       simple_knn.distCUDA2 (create_from_pcd's initial scales) at 250k, 1M and 4M points on a uniform cube and
+            on a Gaussian cloud with a 10% skybox shell at 10x its radius, the scenes alternated from round to round;
+            beside them the all-pairs torch restatement (tests/knn_ref.py) at 250k, timed once.
   stream    train_post.py's SPT cache over the same hierarchy: SPT construction (host code), then a camera path
             of views through SPTCache.step (coarse cut, cache bookkeeping, SPT cut, write-back and load of the
             six parameters and twelve Adam moments to and from pinned host storage) and the dense Adam step of
@@ -208,6 +211,55 @@ def bench_morton(xyz):
                 alg_GBs=round(alg / (ms * 1e-3) / 1e9, 1))
 
 
+def knn_scene(name, P, seed=0):
+    g = torch.Generator(device=DEV).manual_seed(seed)
+    if name == "cube":
+        return torch.rand((P, 3), device=DEV, generator=g)
+    S_ = P // 10  # cloud + skybox shell, as create_from_pcd makes it (scene/gaussian_model.py:829-838)
+    cloud = torch.randn((P - S_, 3), device=DEV, generator=g)
+    mean = cloud.mean(0)
+    radius = torch.linalg.norm(cloud.max(0)[0] - mean)
+    theta = 2.0 * math.pi * torch.rand(S_, device=DEV, generator=g)
+    phi = torch.arccos(1.0 - 1.4 * torch.rand(S_, device=DEV, generator=g))
+    shell = radius * 10 * torch.stack((torch.cos(theta) * torch.sin(phi), torch.sin(theta) * torch.sin(phi),
+                                       torch.cos(phi)), 1) + mean
+    return torch.cat((shell, cloud)).contiguous()
+
+
+def bench_knn(sizes=(250_000, 1_000_000, 4_000_000), rounds=5, calls=4, restatement_P=250_000):
+    from simple_knn._C import distCUDA2, plan
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from knn_ref import knn_ref
+    names = ("cube", "cloud_skybox")
+    out = dict(workload="simple_knn.distCUDA2: mean squared distance to the 3 nearest other points", sizes={})
+    for P in sizes:
+        pts = {n: knn_scene(n, P) for n in names}
+        for n in names:  # settle: code objects, allocator
+            for _ in range(3):
+                distCUDA2(pts[n])
+        torch.cuda.synchronize()
+        ms = {n: [] for n in names}
+        for _ in range(rounds):  # alternate the scenes so that drift of the shared host hits both alike
+            for n in names:
+                ms[n].append(timed(lambda: distCUDA2(pts[n]), iters=calls, warmup=1))
+        out["sizes"][str(P)] = dict(plan=plan(P), **{n: dict(ms=round(float(np.median(ms[n])), 4),
+                                                             ms_min=round(min(ms[n]), 4), ms_max=round(max(ms[n]), 4),
+                                                             ns_per_point=round(float(np.median(ms[n])) * 1e6 / P, 3))
+                                                     for n in names})
+        if P == restatement_P:
+            knn_ref(pts["cube"][:4096], DEV)  # settle
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            ref = knn_ref(pts["cube"], DEV)
+            torch.cuda.synchronize()
+            out["restatement"] = dict(workload=f"all-pairs torch restatement, cube, {P} points, one run",
+                                      ms=round((time.perf_counter() - t0) * 1e3, 1),
+                                      bitwise_equal=bool(torch.equal(ref.view(torch.int32),
+                                                                     distCUDA2(pts["cube"]).view(torch.int32))))
+        del pts
+    return out
+
+
 def bench_stream(P, views=12):
     from hlgs_core import spt
     from hlgs_core.spt_cache import NAMES, SPTCache
@@ -267,6 +319,7 @@ def main():
     ap.add_argument("--W", type=int, default=1920)
     ap.add_argument("--H", type=int, default=1080)
     ap.add_argument("--only", default="alt,loss,adam,lod")
+    ap.add_argument("--knn-sizes", default="250000,1000000,4000000")
     args = ap.parse_args()
     only = set(args.only.split(","))
     out = dict(device=torch.cuda.get_device_name(0), data="synthetic (seeded PCG64)")
@@ -279,6 +332,8 @@ def main():
     if "lod" in only:
         out["lod"], (xyz, _) = bench_lod(args.P, args.W, args.H, 3)
         out["morton"] = bench_morton(xyz)
+    if "knn" in only:
+        out["knn"] = bench_knn(tuple(int(v) for v in args.knn_sizes.split(",")))
     if "stream" in only:
         out["stream"] = bench_stream(args.P)
     print(json.dumps(out))
