@@ -1050,6 +1050,40 @@ int hlgs_ssim_backward(int C, int H, int W, const float* img1, const float* img2
     return hlgs_ssim_backward_ex(C, H, W, img1, img2, 0, dmaps, coef, grad_img1, stream);
 }
 
+size_t hlgs_photo_scratch_size(int H, int W)
+{
+    if (H <= 0 || W <= 0) return kAlign;
+    return align_up(sizeof(float) * photo_scratch_floats(H, W)) + kAlign;
+}
+
+int hlgs_photo_forward(int H, int W, const float* image, const float* gt, int flags, const float* exposure,
+                       const float* alpha_mask, float* dmaps, void* scratch, float* out, void* stream)
+{
+    if (H <= 0 || W <= 0) return fail(HLGS_ERR_ARG, "empty image");
+    if (flags & ~HLGS_SSIM_CLAMP1) return fail(HLGS_ERR_ARG, "unknown photometric flags (HLGS_SSIM_CLAMP1 only)");
+    if (!image || !gt || !scratch || !out) return fail(HLGS_ERR_ARG, "missing tensor");
+    hipStream_t s = (hipStream_t)stream;
+    hipGetLastError();
+    launch_photo_forward(H, W, image, gt, exposure, alpha_mask, dmaps, static_cast<float*>(aligned(scratch)), out, s,
+                         (flags & HLGS_SSIM_CLAMP1) != 0);
+    return check_stage(s, false, "photo_forward");
+}
+
+int hlgs_photo_backward(int H, int W, const float* image, const float* gt, int flags, const float* exposure,
+                        const float* alpha_mask, const float* dmaps, const float* coef, float* grad_image,
+                        float* grad_exposure, void* scratch, void* stream)
+{
+    if (H <= 0 || W <= 0) return fail(HLGS_ERR_ARG, "empty image");
+    if (flags & ~HLGS_SSIM_CLAMP1) return fail(HLGS_ERR_ARG, "unknown photometric flags (HLGS_SSIM_CLAMP1 only)");
+    if (!image || !gt || !dmaps || !coef || !grad_image || !scratch) return fail(HLGS_ERR_ARG, "missing tensor");
+    if (grad_exposure && !exposure) return fail(HLGS_ERR_ARG, "grad_exposure without an exposure");
+    hipStream_t s = (hipStream_t)stream;
+    hipGetLastError();
+    launch_photo_backward(H, W, image, gt, exposure, alpha_mask, dmaps, coef, grad_image, grad_exposure,
+                          static_cast<float*>(aligned(scratch)), s, (flags & HLGS_SSIM_CLAMP1) != 0);
+    return check_stage(s, false, "photo_backward");
+}
+
 size_t hlgs_depth_l1_scratch_size(int64_t n)
 {
     return align_up(sizeof(float) * (size_t)depth_l1_blocks(n > 0 ? n : 1)) + kAlign;

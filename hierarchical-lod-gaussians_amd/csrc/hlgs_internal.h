@@ -335,6 +335,12 @@ void launch_ssim_forward(int C, int H, int W, const float* img1, const float* im
                          float* partial, float* out, hipStream_t s, bool clamp1);
 void launch_ssim_backward(int C, int H, int W, const float* img1, const float* img2, const float* abc,
                           const float* coef, float* grad1, hipStream_t s, bool clamp1);
+size_t photo_scratch_floats(int H, int W);
+void launch_photo_forward(int H, int W, const float* image, const float* gt, const float* expo, const float* amask,
+                          float* abc, float* partial, float* out, hipStream_t s, bool clamp1);
+void launch_photo_backward(int H, int W, const float* image, const float* gt, const float* expo, const float* amask,
+                           const float* abc, const float* coef, float* grad, float* grad_expo, float* partial,
+                           hipStream_t s, bool clamp1);
 int depth_l1_blocks(long n);
 void launch_depth_l1_forward(long n, const float* inv, const float* mono, const float* mask, float* partial,
                              float* out, hipStream_t s);

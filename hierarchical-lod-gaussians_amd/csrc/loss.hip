@@ -1,5 +1,7 @@
 // loss.hip -- fused photometric loss kernels for gfx950: SSIM (11x11 Gaussian window, sigma 1.5) with its
-// gradient, L1 and the masked inverse-depth L1 of the training step.
+// gradient, L1 and the masked inverse-depth L1 of the training step; and the "post" path (ExpoCol below), which applies
+// the view's trained exposure, the clamp and the alpha mask to a 3-channel render as the same kernels load it, returns
+// the exposure's gradient, and adds the per-plane squared error for the PSNR of the evaluation loops.
 //
 // Reference semantics: utils/loss_utils.py:17-63 (l1_loss, ssim/_ssim: F.conv2d with the window of
 // create_window, zero padding window_size // 2, C1 = 0.01^2, C2 = 0.03^2, map mean), the un-vendored
@@ -115,28 +117,91 @@ __device__ __forceinline__ void col_sums8(const float* hs_m, const Win11& win, i
 // (gaussian_renderer/__init__.py:142, 612) folded into the loss's own loads; NaN stays NaN, as torch.clamp keeps it.
 __device__ __forceinline__ float clamp01(float v) { return v < 0.f ? 0.f : (v > 1.f ? 1.f : v); }
 
-template <bool TRAIN, bool CLAMP>
+// The "post" path: what the reference does to a 3-channel render between the rasterizer and the loss, applied to the
+// raw image as it is loaded (no transformed image is ever stored).  Per pixel p and output channel c
+//   t_c  = raw_0 E[0][c] + raw_1 E[1][c] + raw_2 E[2][c] + E[c][3]   the view's trained exposure, row-major (3, 4):
+//          matmul(img.permute(1, 2, 0), E[:3, :3]).permute(2, 0, 1) + E[:3, 3, None, None]
+//          (gaussian_renderer/__init__.py:139-141); t_c = raw_c without an exposure
+//   x'_c = m (CLAMP ? clamp01(t_c) : t_c)                             the clamp (:142), then image *= alpha_mask
+//          (train_single.py:102-104); m = 1 without a mask
+// and x' stands where clamp01(img1) stands in the plain kernels: in the SSIM moments, the L1 term and the backward's
+// xv.  The horizontal-pass loads, the forward's per-pixel L1 reload and the backward all form x' with expo_acc in the
+// order bias, plane 0, 1, 2 and then post_finish, so they see the same bits.  An identity exposure and a mask of ones
+// reproduce the plain kernels' values exactly (1 x + 0 y + 0 z + 0 and 1 x are exact).
+struct ExpoCol {
+    float e0, e1, e2, b;  // column c of E's 3x3 block and the bias of channel c
+};
+__device__ __forceinline__ ExpoCol expo_col(const float* __restrict__ E, int c)
+{
+    return ExpoCol{E[c], E[4 + c], E[8 + c], E[4 * c + 3]};
+}
+__device__ __forceinline__ float expo_acc(float acc, float r, float e) { return fmaf(r, e, acc); }
+__device__ __forceinline__ float expo_mix(float r0, float r1, float r2, const ExpoCol& e)
+{
+    return expo_acc(expo_acc(expo_acc(e.b, r0, e.e0), r1, e.e1), r2, e.e2);
+}
+template <bool CLAMP>
+__device__ __forceinline__ float post_finish(float tc, float m)
+{
+    return __fmul_rn(m, CLAMP ? clamp01(tc) : tc);  // one rounded product: never contracted into a later sum
+}
+
+// POST = 0: the plain kernel (img1 is C planes; expo, amask unused; partial holds 2 sums per block).
+// POST = 1, 2: the post path over the 3 planes of img1 without (1) or with (2) the exposure; amask may be NULL; partial
+// holds 3 sums per block, the third being sum (x' - y)^2 for the PSNR of the evaluation loops.
+template <bool TRAIN, bool CLAMP, int POST>
 __global__ void __launch_bounds__(kQThreads) k_ssim_fwd(int H, int W, const float* __restrict__ img1,
                                                         const float* __restrict__ img2, int valid, Win11 win,
-                                                        float* __restrict__ abc, float* __restrict__ partial)
+                                                        float* __restrict__ abc, float* __restrict__ partial,
+                                                        const float* __restrict__ expo,
+                                                        const float* __restrict__ amask)
 {
     __shared__ __attribute__((aligned(16))) float hs[5][kQRows * kQS];
-    __shared__ float red[2][kQThreads / 64];
+    __shared__ float red[POST ? 3 : 2][kQThreads / 64];
     const int ch = blockIdx.z;
     const size_t HW = (size_t)H * W;
     const float* x = img1 + ch * HW;
     const float* y = img2 + ch * HW;
     const int x0 = blockIdx.x * kQW, y0 = blockIdx.y * kQH;
     const int t = threadIdx.x;
+    ExpoCol ec{};
+    if (POST == 2) ec = expo_col(expo, ch);
     if (t < kQRows * (kQW / kQSeg)) {
         const int r = t >> 3, c0 = kQSeg * (t & 7);
         const int gy = y0 - kHalo + r, xs = x0 - kHalo + c0;
         float u[kQIn], v[kQIn], f[kQIn];
-        load_run26(x, H, W, gy, xs, u);
-        load_run26(y, H, W, gy, xs, v);
-        if (CLAMP) {
+        if (POST == 0) {
+            load_run26(x, H, W, gy, xs, u);
+            load_run26(y, H, W, gy, xs, v);
+            if (CLAMP) {
 #pragma unroll
-            for (int i = 0; i < kQIn; i++) u[i] = clamp01(u[i]);
+                for (int i = 0; i < kQIn; i++) u[i] = clamp01(u[i]);
+            }
+        } else {
+            if (POST == 2) {  // the three raw planes accumulate into the one run
+                load_run26(img1, H, W, gy, xs, f);
+#pragma unroll
+                for (int i = 0; i < kQIn; i++) u[i] = expo_acc(ec.b, f[i], ec.e0);
+                load_run26(img1 + HW, H, W, gy, xs, f);
+#pragma unroll
+                for (int i = 0; i < kQIn; i++) u[i] = expo_acc(u[i], f[i], ec.e1);
+                load_run26(img1 + 2 * HW, H, W, gy, xs, f);
+#pragma unroll
+                for (int i = 0; i < kQIn; i++) u[i] = expo_acc(u[i], f[i], ec.e2);
+            } else {
+                load_run26(x, H, W, gy, xs, u);
+            }
+            // zero padding is of x', not of raw (outside the image t_c is the bias, not 0): the mask run is 0 there
+            if (amask) {
+                load_run26(amask, H, W, gy, xs, f);
+            } else {
+                const bool rowin = gy >= 0 && gy < H;
+#pragma unroll
+                for (int i = 0; i < kQIn; i++) f[i] = rowin && xs + i >= 0 && xs + i < W ? 1.f : 0.f;
+            }
+#pragma unroll
+            for (int i = 0; i < kQIn; i++) u[i] = post_finish<CLAMP>(u[i], f[i]);
+            load_run26(y, H, W, gy, xs, v);
         }
         float* row = &hs[0][r * kQS + c0];
         row_sums16(u, win, row);
@@ -157,7 +222,7 @@ __global__ void __launch_bounds__(kQThreads) k_ssim_fwd(int H, int W, const floa
 #pragma unroll
     for (int m = 0; m < 5; m++) col_sums8(hs[m], win, c, q, mo[m]);
     const int px = x0 + c;
-    float s_map = 0.f, s_l1 = 0.f;
+    float s_map = 0.f, s_l1 = 0.f, s_sq = 0.f;
     if (px < W) {
 #pragma unroll
         for (int jj = 0; jj < kQR; jj++) {
@@ -172,7 +237,14 @@ __global__ void __launch_bounds__(kQThreads) k_ssim_fwd(int H, int W, const floa
             const float cc = mu1_sq + mu2_sq + kC1, d = s11 + s22 + kC2;
             const float fm = (a * b) / (cc * d);
             if (counted) s_map += fm;
-            s_l1 += fabsf((CLAMP ? clamp01(x[pid]) : x[pid]) - y[pid]);
+            if (POST == 0) {
+                s_l1 += fabsf((CLAMP ? clamp01(x[pid]) : x[pid]) - y[pid]);
+            } else {
+                const float tc = POST == 2 ? expo_mix(img1[pid], img1[HW + pid], img1[2 * HW + pid], ec) : x[pid];
+                const float df = post_finish<CLAMP>(tc, amask ? amask[pid] : 1.f) - y[pid];
+                s_l1 += fabsf(df);
+                s_sq = fmaf(df, df, s_sq);
+            }
             if (TRAIN) {
                 float A = 0.f, B = 0.f, C = 0.f;
                 if (counted) {
@@ -193,17 +265,38 @@ __global__ void __launch_bounds__(kQThreads) k_ssim_fwd(int H, int W, const floa
     for (int off = 32; off > 0; off >>= 1) {
         s_map += __shfl_xor(s_map, off, 64);
         s_l1 += __shfl_xor(s_l1, off, 64);
+        if (POST) s_sq += __shfl_xor(s_sq, off, 64);
     }
     const int wave = t >> 6;
-    if ((t & 63) == 0) { red[0][wave] = s_map; red[1][wave] = s_l1; }
+    if ((t & 63) == 0) {
+        red[0][wave] = s_map;
+        red[1][wave] = s_l1;
+        if (POST) red[2][wave] = s_sq;
+    }
     __syncthreads();
     if (t == 0) {
-        float sa = 0.f, sb = 0.f;
-        for (int i = 0; i < kQThreads / 64; i++) { sa += red[0][i]; sb += red[1][i]; }
+        float sa = 0.f, sb = 0.f, sc = 0.f;
+        for (int i = 0; i < kQThreads / 64; i++) {
+            sa += red[0][i];
+            sb += red[1][i];
+            if (POST) sc += red[2][i];
+        }
         const size_t blk = ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-        partial[2 * blk] = sa;
-        partial[2 * blk + 1] = sb;
+        partial[(POST ? 3 : 2) * blk] = sa;
+        partial[(POST ? 3 : 2) * blk + 1] = sb;
+        if (POST) partial[3 * blk + 2] = sc;
     }
+}
+
+// The post backward's gradient of one pixel before any gate: c0 * dSSIM-map-sum/dxv + c1 * sign(xv - yv), from the three
+// window sums g of the A, B, C maps -- k_ssim_bwd's expression, term for term (k_ssim_bwd keeps its own text so that
+// its code does not change).
+__device__ __forceinline__ float pixel_grad(float g0, float g1, float g2, float xv, float yv, float c0, float c1)
+{
+    const float dssim = g0 + 2.f * xv * g1 + yv * g2;
+    const float diff = xv - yv;
+    const float sgn = diff > 0.f ? 1.f : (diff < 0.f ? -1.f : 0.f);  // torch.abs backward: sign, 0 at 0
+    return c0 * dssim + c1 * sgn;
 }
 
 // grad1 = coef[0] * dSSIM-map-sum/dx + coef[1] * sign(x - y)  (coefficients on the device: no host sync).  CLAMP: x is
@@ -251,6 +344,130 @@ __global__ void __launch_bounds__(kQThreads) k_ssim_bwd(int H, int W, const floa
         const float gv = c0 * dssim + c1 * sgn;
         grad1[pid] = !CLAMP || (raw >= 0.f && raw <= 1.f) ? gv : 0.f;
     }
+}
+
+// The post path's backward (see ExpoCol above).  With gv_c = pixel_grad at xv = x'_c:
+//   g_c = gv_c m [0 <= t_c <= 1 if CLAMP]   (false at NaN, as torch's clamp backward)
+//   d raw_k = sum_c E[k][c] g_c,   dE[k][c] = sum_p raw_k(p) g_c(p),   dE[c][3] = sum_p g_c(p)
+// The channel mix crosses the planes, so one workgroup walks the three channels of its 128 x 16 tile in turn through
+// the same LDS, keeps the 8 x 3 g values of each thread in registers, writes d raw, and reduces its 12 sums to one
+// partial (shuffles, then one lane per wave, laid out as E); k_reduce_expo_grad sums the partials.  No float atomics:
+// d raw and dE do not change from run to run.  de_partial = NULL skips the 12 sums.  EXPO = false: d raw_c = g_c.
+template <bool CLAMP, bool EXPO>
+__global__ void __launch_bounds__(kQThreads) k_photo_bwd(int H, int W, const float* __restrict__ img1,
+                                                         const float* __restrict__ img2, const float* __restrict__ abc,
+                                                         Win11 win, const float* __restrict__ coef,
+                                                         const float* __restrict__ expo,
+                                                         const float* __restrict__ amask, float* __restrict__ grad1,
+                                                         float* __restrict__ de_partial)
+{
+    __shared__ __attribute__((aligned(16))) float hs[3][kQRows * kQS];
+    __shared__ float red[12][kQThreads / 64];
+    const size_t HW = (size_t)H * W;
+    const int x0 = blockIdx.x * kQW, y0 = blockIdx.y * kQH;
+    const int t = threadIdx.x;
+    const int c = t & (kQW - 1), q = t / kQW;
+    const int px = x0 + c;
+    const int rows = px < W ? min(kQR, H - (y0 + kQR * q)) : 0;  // this thread's pixels: rows [0, rows) of its 8
+    const size_t pix0 = (size_t)(y0 + kQR * q) * W + px;
+    float rw[3][kQR], mk[kQR], gk[3][kQR];
+#pragma unroll
+    for (int jj = 0; jj < kQR; jj++) {
+        const bool in = jj < rows;
+        const size_t pix = pix0 + (size_t)jj * W;
+        mk[jj] = in && amask ? amask[pix] : 1.f;
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            rw[k][jj] = EXPO && in ? img1[k * HW + pix] : 0.f;
+            gk[k][jj] = 0.f;
+        }
+    }
+    const float c0 = coef[0], c1 = coef[1];
+#pragma unroll
+    for (int ch = 0; ch < 3; ch++) {
+        if (ch) __syncthreads();  // the vertical pass of the previous channel has read hs
+        const float* maps = abc + (size_t)ch * 3 * HW;
+        if (t < kQRows * (kQW / kQSeg)) {
+            const int r = t >> 3, s0 = kQSeg * (t & 7);
+            const int gy = y0 - kHalo + r, xs = x0 - kHalo + s0;
+            float f[kQIn];
+#pragma unroll
+            for (int m = 0; m < 3; m++) {
+                load_run26(maps + m * HW, H, W, gy, xs, f);
+                row_sums16(f, win, &hs[m][r * kQS + s0]);
+            }
+        }
+        __syncthreads();
+        float g[3][kQR];
+#pragma unroll
+        for (int m = 0; m < 3; m++) col_sums8(hs[m], win, c, q, g[m]);
+        ExpoCol ec{};
+        if (EXPO) ec = expo_col(expo, ch);
+#pragma unroll
+        for (int jj = 0; jj < kQR; jj++) {
+            if (jj >= rows) break;
+            const size_t pid = (size_t)ch * HW + pix0 + (size_t)jj * W;
+            const float tc = EXPO ? expo_mix(rw[0][jj], rw[1][jj], rw[2][jj], ec) : img1[pid];
+            const float yv = img2[pid];
+            const float xv = post_finish<CLAMP>(tc, mk[jj]);
+            const float gv = pixel_grad(g[0][jj], g[1][jj], g[2][jj], xv, yv, c0, c1);
+            const float gc = !CLAMP || (tc >= 0.f && tc <= 1.f) ? __fmul_rn(gv, mk[jj]) : 0.f;
+            if (EXPO) gk[ch][jj] = gc;
+            else grad1[pid] = gc;
+        }
+    }
+    if (!EXPO) return;
+    float e[12];
+#pragma unroll
+    for (int i = 0; i < 12; i++) e[i] = expo[i];
+#pragma unroll
+    for (int jj = 0; jj < kQR; jj++) {
+        if (jj >= rows) break;
+        const size_t pix = pix0 + (size_t)jj * W;
+#pragma unroll
+        for (int k = 0; k < 3; k++)
+            grad1[k * HW + pix] = fmaf(e[4 * k + 2], gk[2][jj],
+                                       fmaf(e[4 * k + 1], gk[1][jj], __fmul_rn(e[4 * k], gk[0][jj])));
+    }
+    if (!de_partial) return;  // the caller wants no exposure gradient (the same for every thread)
+    float sum[12];
+#pragma unroll
+    for (int i = 0; i < 12; i++) sum[i] = 0.f;
+#pragma unroll
+    for (int jj = 0; jj < kQR; jj++) {  // rows past `rows` hold rw = gk = 0
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+#pragma unroll
+            for (int cc = 0; cc < 3; cc++) sum[4 * k + cc] = fmaf(rw[k][jj], gk[cc][jj], sum[4 * k + cc]);
+            sum[4 * k + 3] += gk[k][jj];
+        }
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+#pragma unroll
+        for (int i = 0; i < 12; i++) sum[i] += __shfl_xor(sum[i], off, 64);
+    }
+    if ((t & 63) == 0) {
+#pragma unroll
+        for (int i = 0; i < 12; i++) red[i][t >> 6] = sum[i];
+    }
+    __syncthreads();
+    if (t < 12) {
+        float s = 0.f;
+        for (int i = 0; i < kQThreads / 64; i++) s += red[t][i];
+        de_partial[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 12 + t] = s;
+    }
+}
+
+// One block of 12 waves: wave w sums entry w of the n workgroup partials (12 floats each) in double, each lane its
+// indices in order, then a shuffle tree; d_expo is laid out as the exposure.
+__global__ void __launch_bounds__(768) k_reduce_expo_grad(int n, const float* __restrict__ partial,
+                                                          float* __restrict__ d_expo)
+{
+    const int w = threadIdx.x >> 6;
+    double a = 0.0;
+    for (int i = threadIdx.x & 63; i < n; i += 64) a += (double)partial[(size_t)i * 12 + w];
+    for (int off = 32; off > 0; off >>= 1) a += __shfl_xor(a, off, 64);
+    if ((threadIdx.x & 63) == 0) d_expo[w] = (float)a;
 }
 
 // mean |(inv - mono) * mask| partial sums; mask may be NULL (= 1).
@@ -306,6 +523,40 @@ __global__ void __launch_bounds__(1024) k_reduce_partials(int n, int stride, con
     }
 }
 
+// One block, the post forward's partials (3 per workgroup, the n workgroups of plane 0 first, then plane 1, plane 2):
+// out[0] = s_map * sum of the SSIM sums, out[1] = s_all * sum of the L1 sums (both over all 3 n workgroups, in the
+// order k_reduce_partials takes them), out[2 + p] = s_plane * sum of plane p's squared-difference sums.  In double,
+// in a fixed order.
+__global__ void __launch_bounds__(1024) k_reduce_photo(int n, const float* __restrict__ partial, double s_map,
+                                                       double s_all, double s_plane, float* __restrict__ out)
+{
+    __shared__ double red[5][16];
+    double a[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int i = threadIdx.x; i < 3 * n; i += 1024) {
+        a[0] += (double)partial[(size_t)i * 3];
+        a[1] += (double)partial[(size_t)i * 3 + 1];
+        const double sq = (double)partial[(size_t)i * 3 + 2];
+        const int p = i / n;
+        a[2] += p == 0 ? sq : 0.0;
+        a[3] += p == 1 ? sq : 0.0;
+        a[4] += p == 2 ? sq : 0.0;
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+#pragma unroll
+        for (int k = 0; k < 5; k++) a[k] += __shfl_xor(a[k], off, 64);
+    }
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int k = 0; k < 5; k++) red[k][threadIdx.x >> 6] = a[k];
+    }
+    __syncthreads();
+    if (threadIdx.x < 5) {
+        double s = 0.0;
+        for (int i = 0; i < 16; i++) s += red[threadIdx.x][i];
+        out[threadIdx.x] = (float)(s * (threadIdx.x == 0 ? s_map : (threadIdx.x == 1 ? s_all : s_plane)));
+    }
+}
+
 static Win11 gauss_window()
 {
     // utils/loss_utils.py:23-25: exp(-(x - 5)^2 / (2 sigma^2)) in double, stored as float32, normalised in float32
@@ -332,8 +583,9 @@ void launch_ssim_forward(int C, int H, int W, const float* img1, const float* im
 {
     const dim3 g = ssim_grid(C, H, W);
     const Win11 w = gauss_window();
-#define HLGS_SSIMF(TR, CL) hipLaunchKernelGGL((k_ssim_fwd<TR, CL>), g, dim3(kQThreads), 0, s, H, W, img1, img2, valid, w, \
-                                              abc, partial)
+    const float* none = nullptr;
+#define HLGS_SSIMF(TR, CL) hipLaunchKernelGGL((k_ssim_fwd<TR, CL, 0>), g, dim3(kQThreads), 0, s, H, W, img1, img2, valid, \
+                                              w, abc, partial, none, none)
     if (abc) { if (clamp1) HLGS_SSIMF(true, true); else HLGS_SSIMF(true, false); }
     else { if (clamp1) HLGS_SSIMF(false, true); else HLGS_SSIMF(false, false); }
 #undef HLGS_SSIMF
@@ -352,6 +604,45 @@ void launch_ssim_backward(int C, int H, int W, const float* img1, const float* i
     else
         hipLaunchKernelGGL(k_ssim_bwd<false>, ssim_grid(C, H, W), dim3(kQThreads), 0, s, H, W, img1, img2, abc,
                            gauss_window(), coef, grad1);
+}
+
+size_t photo_scratch_floats(int H, int W)
+{
+    const dim3 g = ssim_grid(3, H, W);  // forward: 3 sums per workgroup of 3 planes; backward: 12 per tile
+    return (size_t)g.x * g.y * 12;
+}
+
+void launch_photo_forward(int H, int W, const float* image, const float* gt, const float* expo, const float* amask,
+                          float* abc, float* partial, float* out, hipStream_t s, bool clamp1)
+{
+    const dim3 g = ssim_grid(3, H, W);
+    const Win11 w = gauss_window();
+#define HLGS_PHOTOF(TR, CL, PO) hipLaunchKernelGGL((k_ssim_fwd<TR, CL, PO>), g, dim3(kQThreads), 0, s, H, W, image, gt, 0, \
+                                                   w, abc, partial, expo, amask)
+#define HLGS_PHOTOF2(TR, CL) do { if (expo) HLGS_PHOTOF(TR, CL, 2); else HLGS_PHOTOF(TR, CL, 1); } while (0)
+    if (abc) { if (clamp1) HLGS_PHOTOF2(true, true); else HLGS_PHOTOF2(true, false); }
+    else { if (clamp1) HLGS_PHOTOF2(false, true); else HLGS_PHOTOF2(false, false); }
+#undef HLGS_PHOTOF2
+#undef HLGS_PHOTOF
+    const double n_plane = (double)H * W;
+    hipLaunchKernelGGL(k_reduce_photo, dim3(1), dim3(1024), 0, s, (int)(g.x * g.y), partial, 1.0 / (3.0 * n_plane),
+                       1.0 / (3.0 * n_plane), 1.0 / n_plane, out);
+}
+
+void launch_photo_backward(int H, int W, const float* image, const float* gt, const float* expo, const float* amask,
+                           const float* abc, const float* coef, float* grad, float* grad_expo, float* partial,
+                           hipStream_t s, bool clamp1)
+{
+    const dim3 g = ssim_grid(1, H, W);
+    const Win11 w = gauss_window();
+    float* dep = grad_expo ? partial : nullptr;
+#define HLGS_PHOTOB(CL, EX) hipLaunchKernelGGL((k_photo_bwd<CL, EX>), g, dim3(kQThreads), 0, s, H, W, image, gt, abc, w, \
+                                               coef, expo, amask, grad, dep)
+    if (expo) { if (clamp1) HLGS_PHOTOB(true, true); else HLGS_PHOTOB(false, true); }
+    else { if (clamp1) HLGS_PHOTOB(true, false); else HLGS_PHOTOB(false, false); }
+#undef HLGS_PHOTOB
+    if (grad_expo)
+        hipLaunchKernelGGL(k_reduce_expo_grad, dim3(1), dim3(768), 0, s, (int)(g.x * g.y), partial, grad_expo);
 }
 
 int depth_l1_blocks(long n) { return (int)std::min<long>(2048, (n + 255) / 256); }

@@ -28,6 +28,10 @@
  *        Python loops over torch ops
  *   hlgs_adam_update                        <- adamUpdate, submodules/alt-rasterizer/rasterize_points.cu:255-281
  *        (kernel cuda_rasterizer/adam.cu:9-36), bound as _C.adamUpdate (ext.cpp:19)
+ *   hlgs_photo_forward/_backward            <- the torch ops between the rasterizer and the loss: the exposure of
+ *        render(..., use_trained_exp=True) (gaussian_renderer/__init__.py:139-141), rendered_image.clamp(0, 1) (:142)
+ *        and image *= alpha_mask (train_single.py:102-104), with the loss of train_single.py:106-110 and the PSNR
+ *        of utils/image_utils.py:17-19
  *
  * The alt rasterizer (submodules/alt-rasterizer: RasterizeGaussiansCUDA rasterize_points.cu:44-137 and
  * RasterizeGaussiansBackwardCUDA :138-232) goes through the same rasterizer entry points with
@@ -451,6 +455,27 @@ int hlgs_ssim_forward_ex(int C, int H, int W, const float* img1, const float* im
                          void* scratch, float* out, void* stream);
 int hlgs_ssim_backward_ex(int C, int H, int W, const float* img1, const float* img2, int flags, const float* dmaps,
                           const float* coef, float* grad_img1, void* stream);
+/* The photometric forward and backward of a 3-channel render with what the reference does to it between the rasterizer
+ * and the loss applied as the image is loaded -- nothing transformed is stored.  Per pixel p and channel c
+ *   t_c  = image_0 E[0][c] + image_1 E[1][c] + image_2 E[2][c] + E[c][3]   (exposure given, else t_c = image_c)
+ *   x'_c = m (CLAMP1 ? clamp(t_c, 0, 1) : t_c)                             (alpha_mask given, else m = 1)
+ * E (12 device floats, row-major (3, 4)) is the view's trained exposure of render(..., use_trained_exp=True),
+ * torch.matmul(img.permute(1, 2, 0), E[:3, :3]).permute(2, 0, 1) + E[:3, 3, None, None]
+ * (gaussian_renderer/__init__.py:139-141); the clamp is :142 (flags = HLGS_SSIM_CLAMP1, the only flag accepted);
+ * m (H x W) is the alpha mask of train_single.py:102-104 / train_coarse.py:122-125 / render_hierarchy.py:108-112.
+ * Zero padding is of x'.  out (device, 5 floats) = (mean SSIM of x' against gt, mean |x' - gt|, mean (x' - gt)^2 of
+ * planes 0, 1, 2 -- the PSNR of utils/image_utils.py:17-19 follows from the last three).  dmaps (9 x H x W, or NULL: no
+ * gradient maps) as hlgs_ssim_forward's.  scratch: hlgs_photo_scratch_size bytes, for either call.
+ * Backward, with gv_c = coef[0] d(sum of the SSIM map)/d x'_c + coef[1] sign(x'_c - gt_c) and
+ * g_c = gv_c m [0 <= t_c <= 1 under CLAMP1]:  grad_image_k = sum_c E[k][c] g_c (= g_k without an exposure);
+ * grad_exposure (12 floats laid out as E, or NULL: not computed) [k][c] = sum_p image_k g_c, [c][3] = sum_p g_c.
+ * No atomics: both gradients are bitwise reproducible.  Pass the same flags, exposure and mask to both calls. */
+size_t hlgs_photo_scratch_size(int H, int W);
+int hlgs_photo_forward(int H, int W, const float* image, const float* gt, int flags, const float* exposure,
+                       const float* alpha_mask, float* dmaps, void* scratch, float* out, void* stream);
+int hlgs_photo_backward(int H, int W, const float* image, const float* gt, int flags, const float* exposure,
+                        const float* alpha_mask, const float* dmaps, const float* coef, float* grad_image,
+                        float* grad_exposure, void* scratch, void* stream);
 /* Depth term of train_single.py:111-118: out[0] = mean |(invdepth - mono) * mask| over n values (mask may be
  * NULL); backward grad = coef[0] * sign((invdepth - mono) * mask) * mask. */
 size_t hlgs_depth_l1_scratch_size(int64_t n);

@@ -7,6 +7,9 @@
             lerp's backward: each stage separately and the whole step inclusive.
   alt       the alt rasterizer (train_post.py's default) on config #2: forward + backward Mpix/s.
   loss      photometric_loss (L1 + D-SSIM + masked inverse-depth L1) forward + backward on a 1080p view.
+  loss_exp  the same loss for a view with a trained (3, 4) exposure and an alpha mask (clamp_image=True), gradients to
+            the image and the exposure: the fused call beside the torch composition it replaces, alternated, three
+            runs each.
   adam      SparseGaussianAdam.step over 1M Gaussians (59 floats each, six parameter groups), half visible.
   morton    get_morton_indices over the hierarchy's nodes.
   knn       simple_knn.distCUDA2 (create_from_pcd's initial scales) at 250k, 1M and 4M points on a uniform cube and
@@ -111,6 +114,45 @@ def bench_loss(W, H):
     alg = N * (24 + 36 + 60 + 12) + N * (12 + 12 + 4)
     return dict(workload=f"photometric loss (L1 + D-SSIM + depth L1), 3x{H}x{W}, fwd+bwd", ms=round(ms, 4),
                 alg_GBs=round(alg / (ms * 1e-3) / 1e9, 1), hbm_frac=round(alg / (ms * 1e-3) / 1e9 / HBM, 3))
+
+
+def bench_loss_exp(W, H, legs=("fused", "composed"), runs=3):
+    """The loss of a view with a trained exposure and an alpha mask, forward + backward to the image and the exposure:
+    `fused` is photometric_loss(..., clamp_image=True, exposure=E, alpha_mask=m); `composed` is what a caller wrote
+    before it, in the same process -- the reference's torch expression (gaussian_renderer/__init__.py:139-141),
+    .clamp(0, 1), * mask, then the plain photometric_loss.  Each run is timed()'s median after its own untimed settle
+    steps; the legs alternate, `runs` runs each."""
+    from hlgs_core import loss
+    rng = np.random.default_rng(0)
+    img = torch.tensor(rng.uniform(-0.3, 1.3, (3, H, W)).astype(np.float32), device=DEV, requires_grad=True)
+    mask = torch.tensor(rng.uniform(0, 1, (1, H, W)).astype(np.float32), device=DEV)
+    gt = torch.tensor(rng.uniform(0, 1, (3, H, W)).astype(np.float32), device=DEV) * mask
+    E0 = np.eye(3, 4) + np.concatenate([0.15 * rng.standard_normal((3, 3)), 0.05 * rng.standard_normal((3, 1))], 1)
+    E = torch.tensor(E0.astype(np.float32), device=DEV, requires_grad=True)
+
+    def fused():
+        img.grad = E.grad = None
+        loss.photometric_loss(img, gt, 0.2, clamp_image=True, exposure=E, alpha_mask=mask)[0].backward()
+
+    def composed():
+        img.grad = E.grad = None
+        x = torch.matmul(img.permute(1, 2, 0), E[:3, :3]).permute(2, 0, 1) + E[:3, 3, None, None]
+        loss.photometric_loss(x.clamp(0, 1) * mask, gt, 0.2)[0].backward()
+
+    fns = dict(fused=fused, composed=composed)
+    ms = {k: [] for k in legs}
+    for _ in range(runs):
+        for k in legs:
+            ms[k].append(round(timed(fns[k]), 4))
+    out = dict(workload=f"photometric loss with exposure (3, 4), clamp and alpha mask, 3x{H}x{W}, fwd+bwd",
+               runs_ms=ms, min_ms={k: min(v) for k, v in ms.items()}, max_ms={k: max(v) for k, v in ms.items()})
+    if "fused" in legs:
+        N = W * H
+        # algorithmic HBM bytes of the fused leg: fwd reads image, gt and mask (28 B/px) and writes the maps (36 B/px);
+        # bwd reads the maps, image, gt and mask (64 B/px) and writes the image gradient (12 B/px)
+        alg = N * (28 + 36 + 64 + 12)
+        out["fused_alg_GBs"] = round(alg / (min(ms["fused"]) * 1e-3) / 1e9, 1)
+    return out
 
 
 def bench_adam(P):
@@ -327,6 +369,8 @@ def main():
         out["alt"] = bench_alt(args.P, args.W, args.H, 3)
     if "loss" in only:
         out["loss"] = bench_loss(args.W, args.H)
+    if "loss_exp" in only:
+        out["loss_exp"] = bench_loss_exp(args.W, args.H)
     if "adam" in only:
         out["adam"] = bench_adam(args.P)
     if "lod" in only:
