@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "hlgs_internal.h"
+#include "hlgs_rng.h"
 
 namespace hlgs {
 // The process-wide test switches, read once per frame (frame_opts) and never inside one.
@@ -617,6 +618,59 @@ int hlgs_compute_relocation(int P, const float* opacity_old, const float* scale_
     hipGetLastError();
     launch_relocation(P, opacity_old, scale_old, N, binoms, n_max, opacity_new, scale_new, s);
     return check_stage(s, false, "compute_relocation");
+}
+
+// ---------------------------------------------------------------- MCMC densification (mcmc.hip)
+int hlgs_rng_uniform_host(uint64_t seed, uint32_t stream, uint64_t first_index, int64_t n, double* out_host)
+{
+    if (n < 0) return fail(HLGS_ERR_ARG, "n < 0");
+    if (n && !out_host) return fail(HLGS_ERR_ARG, "missing output");
+    for (int64_t i = 0; i < n; i++) out_host[i] = rng_uniform53(seed, stream, first_index + (uint64_t)i);
+    return HLGS_OK;
+}
+
+int hlgs_rng_fill(int kind, uint64_t seed, uint32_t stream, uint64_t first_index, int64_t n, void* out, void* hip_stream)
+{
+    if (kind != HLGS_RNG_UNIFORM64 && kind != HLGS_RNG_NORMAL32) return fail(HLGS_ERR_ARG, "unknown kind");
+    if (n < 0) return fail(HLGS_ERR_ARG, "n < 0");
+    if (n == 0) return HLGS_OK;
+    if (!out) return fail(HLGS_ERR_ARG, "missing output");
+    hipStream_t s = (hipStream_t)hip_stream;
+    hipGetLastError();
+    launch_rng_fill(kind, seed, stream, first_index, n, out, s);
+    return check_stage(s, false, "rng_fill");
+}
+
+size_t hlgs_mcmc_sample_scratch_size(int64_t n) { return mcmc_sample_scratch_bytes(n); }
+
+int hlgs_mcmc_sample(int64_t n, const void* opacity_base, int64_t stride_bytes, const int* alive, int64_t num,
+                     uint64_t seed, uint32_t stream_id, int* sampled, int* counts, int64_t size, void* scratch,
+                     void* hip_stream)
+{
+    if (n < 0 || num < 0 || size < 0) return fail(HLGS_ERR_ARG, "negative size");
+    if (n > 0x7fffffff || size > 0x7fffffff) return fail(HLGS_ERR_ARG, "rows are int32");
+    if (stride_bytes < 4 || stride_bytes % 4) return fail(HLGS_ERR_ARG, "stride must be a positive multiple of 4 bytes");
+    if (!scratch || (n && !opacity_base) || (num && !sampled) || (size && !counts))
+        return fail(HLGS_ERR_ARG, "missing tensor");
+    if ((uintptr_t)opacity_base % 4) return fail(HLGS_ERR_ARG, "opacity must be 4-byte aligned");
+    hipStream_t s = (hipStream_t)hip_stream;
+    hipGetLastError();
+    if (size) HLGS_TRY_HIP(hipMemsetAsync(counts, 0, sizeof(int) * (size_t)size, s));
+    launch_mcmc_sample(n, opacity_base, stride_bytes, alive, num, seed, stream_id, sampled, counts, size, scratch, s);
+    return check_stage(s, false, "mcmc_sample");
+}
+
+int hlgs_mcmc_noise(int64_t P, int64_t first_row, float* means3D, const float* opacity_raw, const float* scaling_raw,
+                    const float* rotation_raw, const float* noise, double scale, uint64_t seed, uint32_t step,
+                    void* hip_stream)
+{
+    if (P < 0 || first_row < 0) return fail(HLGS_ERR_ARG, "negative size");
+    if (first_row >= P) return HLGS_OK;
+    if (!means3D || !opacity_raw || !scaling_raw || !rotation_raw) return fail(HLGS_ERR_ARG, "missing tensor");
+    hipStream_t s = (hipStream_t)hip_stream;
+    hipGetLastError();
+    launch_mcmc_noise(P, first_row, means3D, opacity_raw, scaling_raw, rotation_raw, noise, scale, seed, step, s);
+    return check_stage(s, false, "mcmc_noise");
 }
 
 int hlgs_activate_forward(int64_t n, const float* opacity_raw, const float* scaling_raw, const float* rotation_raw,

@@ -384,6 +384,17 @@ static_assert(kKnnSortTile % 256 == 0, "a sort tile is whole rounds of the histo
 size_t knn_scratch_bytes(int P);
 void launch_knn(int P, const float* xyz, void* scratch, float* out, hipStream_t s);
 
+// mcmc.hip: opacity-weighted sampling, the position noise and the counter-based numbers of the densification round
+constexpr int kMcmcItems = 2048;  // candidates per block of the sampler's float64 prefix sum (256 threads x 8)
+size_t mcmc_sample_scratch_bytes(int64_t n);
+void launch_mcmc_sample(int64_t n, const void* opacity_base, int64_t stride_bytes, const int* alive, int64_t num,
+                        uint64_t seed, uint32_t stream_id, int* sampled, int* counts, int64_t size, void* scratch,
+                        hipStream_t s);
+void launch_mcmc_noise(int64_t P, int64_t first_row, float* means, const float* op_raw, const float* sc_raw,
+                       const float* rot_raw, const float* noise, double scale, uint64_t seed, uint32_t step,
+                       hipStream_t s);
+void launch_rng_fill(int kind, uint64_t seed, uint32_t stream_id, uint64_t first, int64_t n, void* out, hipStream_t s);
+
 // scan.hip
 void scan_inclusive_u32(const uint32_t* in, uint32_t* out, size_t n, uint32_t* tmp, hipStream_t s);
 

@@ -89,6 +89,12 @@ _SIGS = {
     "hlgs_sh_grad_from_colour": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, C.c_int64, _f, _vp, _vp, _vp]),
     "hlgs_mark_visible": (_i, [_i, _vp, _vp, _vp, _vp, _vp]),
     "hlgs_compute_relocation": (_i, [_i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
+    "hlgs_rng_uniform_host": (_i, [C.c_uint64, C.c_uint32, C.c_uint64, C.c_int64, _vp]),
+    "hlgs_rng_fill": (_i, [_i, C.c_uint64, C.c_uint32, C.c_uint64, C.c_int64, _vp, _vp]),
+    "hlgs_mcmc_sample_scratch_size": (_sz, [C.c_int64]),
+    "hlgs_mcmc_sample": (_i, [C.c_int64, _vp, C.c_int64, _vp, C.c_int64, C.c_uint64, C.c_uint32, _vp, _vp, C.c_int64,
+                              _vp, _vp]),
+    "hlgs_mcmc_noise": (_i, [C.c_int64, C.c_int64, _vp, _vp, _vp, _vp, _vp, C.c_double, C.c_uint64, C.c_uint32, _vp]),
     "hlgs_adam_update": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, C.c_uint32, C.c_uint32, _vp]),
     "hlgs_morton_codes": (_i, [_i, _vp, _vp, _vp, _vp, _vp]),
     "hlgs_knn_scratch_size": (_sz, [_i]),

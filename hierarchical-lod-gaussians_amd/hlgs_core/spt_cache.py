@@ -15,6 +15,9 @@ The reference keeps every Gaussian in host storage (GaussianModel.move_storage_t
                                       directly, one packed row per Gaussian (all eighteen rows back to back,
                                       padded to whole 64-byte lines), so the host link carries whole lines
   optimizer step         :786-812  -> hlgs_adam_step (one launch over the six tensors, skybox gradients zeroed)
+  densification          :710-735  -> SPTCache.reset: everything resident written back, the skybox rows resident again,
+                                      optionally on rebuilt SPTs (the round itself is hlgs_core/mcmc.py densify_round)
+  position noise         :868-878  -> SPTCache.add_noise (hlgs_mcmc_noise)
 
   occlusion cull         :344-351  -> optional (occlusion_culling=True, train_post.py's Use_Occlusion_Culling, off by
                                       default there, :83): the coarse cut's upper-tree Gaussians are read from host
@@ -177,12 +180,34 @@ class SPTCache:
                 self.opt_storage[k]["exp_avgs_sqs"].copy_(opt_storage[k]["exp_avgs_sqs"].reshape((G,) + shapes[k]))
         self.device = torch.device(device)
         dev = self.device
+        self._use_bounding_spheres, self._flat_cut = bool(use_bounding_spheres), bool(flat_cut)
+        self._set_spt(spt)
+        self.sky = int(skybox_points)
+        self.rtol, self.atol = float(reuse_tolerance), 0.05
+        self.budget = max_gaussian_budget
+        self.dm_step = distance_multiplier_until_budget
+        self.use_frustum = use_frustum_culling
+        self.occlusion = bool(occlusion_culling)
+        self.last_occlusion = None  # the last occlusion cull's inputs and mask (tests)
+        # per storage row: the resident row holding it while a step's write-back and load run, else -1
+        self.resident_of = torch.full((G,), -1, dtype=torch.int32, device=dev)
+        # the write-back crosses the host link on its own stream, beside the compaction, the load and the rest of
+        # the training step; the next step's load waits for it (wb_done)
+        self.wb_stream = torch.cuda.Stream(device=dev) if dev.type == "cuda" else None
+        self._wb_pending = None  # this step's write-back, launched when the next step starts (_flush_write_back)
+        self._row_shapes = self._widths = None  # per resident tensor: row shape and floats per row (fixed)
+        self._set_skybox_resident()
+
+    def _set_spt(self, spt):
+        """The upper tree, the SPT arrays and the flat cut's walk order of build_hierarchical_spt's dict (the
+        constructor, and reset(spt) after a densification round rebuilt them)."""
+        dev = self.device
         self.nodes = spt["upper_tree_nodes"].to(dev, torch.int32).contiguous()
         # the upper tree's walk order for the flat coarse cut (hlgs_upper_tree_order), or None for the level walk
-        self.cut_order = _spt.upper_tree_order(spt["upper_tree_nodes"], dev) if flat_cut else None
+        self.cut_order = _spt.upper_tree_order(spt["upper_tree_nodes"], dev) if self._flat_cut else None
         self.xyz = spt["upper_tree_xyz"].to(dev, torch.float32).contiguous()
         self.min_distance_squared = spt["min_distance_squared"].to(dev, torch.float32).contiguous()
-        if use_bounding_spheres:
+        if self._use_bounding_spheres:
             self.bounds = spt["bounding_sphere_radii"].to(dev, torch.float32).contiguous()
         else:  # scaling_activation(max(upper_tree_scaling)) * 3.0 (train_post.py:330)
             self.bounds = (torch.exp(torch.max(spt["upper_tree_scaling"].to(dev, torch.float32), dim=-1)[0]) * 3.0)
@@ -191,35 +216,55 @@ class SPTCache:
         self.spt_min = spt["SPT_min"].to(dev, torch.float32).contiguous()
         self.spt_gidx = spt["SPT_gaussian_indices"].to(dev, torch.int32).contiguous()
         self.num_spts = int(self.spt_starts.numel()) - 1
-        self.sky = int(skybox_points)
-        self.rtol, self.atol = float(reuse_tolerance), 0.05
-        self.budget = max_gaussian_budget
-        self.dm_step = distance_multiplier_until_budget
-        self.use_frustum = use_frustum_culling
-        self.occlusion = bool(occlusion_culling)
-        self.last_occlusion = None  # the last occlusion cull's inputs and mask (tests)
-        # setup, train_post.py:208-231
+        self._cut = self._cut_scratch = self._cut_count = None  # sized for the upper tree (plan)
+
+    def _set_skybox_resident(self):
+        """The resident set of train_post.py:208-231 (and :719-735 after a densification round): the skybox rows,
+        loaded from storage, with zero moments and no SPT state."""
+        dev = self.device
         self.render_indices = torch.arange(0, self.sky, device=dev, dtype=torch.int32)
         head = torch.arange(0, self.sky, device=dev, dtype=torch.int32)
         self.params = {k: self._alloc(k, self.sky) for k in NAMES}
         copy_rows_packed([self.params[k] for k in NAMES], self.sky, None, head, self.host, to_host=False)
         self.exp_avgs = {k: torch.zeros_like(self.params[k]) for k in NAMES}
         self.exp_avg_sqs = {k: torch.zeros_like(self.params[k]) for k in NAMES}
-        # per storage row: the resident row holding it while a step's write-back and load run, else -1
-        self.resident_of = torch.full((G,), -1, dtype=torch.int32, device=dev)
-        # the write-back crosses the host link on its own stream, beside the compaction, the load and the rest of
-        # the training step; the next step's load waits for it (wb_done)
-        self.wb_stream = torch.cuda.Stream(device=dev) if dev.type == "cuda" else None
         self.wb_done = None
         self._wb_hold = None
-        self._wb_pending = None  # this step's write-back, launched when the next step starts (_flush_write_back)
-        self._row_shapes = self._widths = None  # per resident tensor: row shape and floats per row (fixed)
-        self._cut = self._cut_scratch = self._cut_count = None
         self.prev_SPT_indices = torch.empty(0, dtype=torch.int32, device=dev)
         self.prev_SPT_distances = torch.empty(0, dtype=torch.float32, device=dev)
         self.prev_SPT_counts = torch.empty(0, dtype=torch.int32, device=dev)
         self.n_loaded = 0
         self.last_plan = None
+
+    # ------------------------------------------------------------ densification (train_post.py:707-735, 868-878)
+    def reset(self, spt=None):
+        """Empty the cache around a densification round (train_post.py:710-735): every resident row and its Adam
+        moments go back to storage (after any pending write-back), the call waits until they have landed, and the
+        resident set is the skybox rows again, loaded from storage with zeroed device moments and no SPT state.
+        spt: build_hierarchical_spt's dict for the changed hierarchy; it replaces the upper tree, the SPT arrays and
+        the flat cut order as the constructor sets them."""
+        self._flush_write_back()
+        R = int(self.render_indices.numel())
+        dev_t = [self.params[k].detach() for k in NAMES] + [self.exp_avgs[k] for k in NAMES] + \
+                [self.exp_avg_sqs[k] for k in NAMES]
+        copy_rows_packed(dev_t, R, None, self.render_indices, self.host, to_host=True)
+        if self.wb_done is not None:
+            self.wb_done.synchronize()
+        torch.cuda.current_stream(self.device).synchronize()
+        self.resident_of.fill_(-1)
+        if spt is not None:
+            self._set_spt(spt)
+        self._set_skybox_resident()
+
+    def add_noise(self, noise_lr, xyz_lr, seed, iteration):
+        """The position noise of train_post.py:868-878 on the resident rows (hlgs_mcmc_noise), after optimizer_step:
+        normals (3 row + c) of (seed, stream = iteration).  noise_lr = MCMC_Noise_LR (0 there by default: a no-op)."""
+        if noise_lr == 0:
+            return
+        from hlgs_core import mcmc
+        p = self.params
+        mcmc.position_noise_(p["xyz"].detach(), p["opacity"].detach(), p["scaling"].detach(), p["rotation"].detach(),
+                             noise_lr, xyz_lr, seed=seed, step=iteration)
 
     def _alloc(self, k, rows):
         return torch.empty((rows,) + tuple(self.storage[k].shape[1:]), dtype=torch.float32, device=self.device)

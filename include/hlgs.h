@@ -32,6 +32,12 @@
  *        render(..., use_trained_exp=True) (gaussian_renderer/__init__.py:139-141), rendered_image.clamp(0, 1) (:142)
  *        and image *= alpha_mask (train_single.py:102-104), with the loss of train_single.py:106-110 and the PSNR
  *        of utils/image_utils.py:17-19
+ *   hlgs_mcmc_sample                        <- GaussianModel._sample_alives, scene/gaussian_model.py:1580-1586
+ *        (torch.multinomial + bincount, on the CPU with host storage), with the sigmoid probabilities of its callers
+ *        relocate_gs (:1614) and add_new_gs (:1714)
+ *   hlgs_mcmc_noise                         <- the position noise of train_post.py:868-878 (op_sigmoid,
+ *        build_scaling_rotation of utils/general_utils.py:82-114, randn_like, bmm)
+ *   hlgs_rng_fill, hlgs_rng_uniform_host    <- the torch generator behind torch.multinomial / torch.randn_like there
  *
  * The alt rasterizer (submodules/alt-rasterizer: RasterizeGaussiansCUDA rasterize_points.cu:44-137 and
  * RasterizeGaussiansBackwardCUDA :138-232) goes through the same rasterizer entry points with
@@ -188,6 +194,46 @@ int hlgs_mark_visible(int P, const float* means3D, const float* viewmatrix, cons
 /* MCMC relocation, utils.cu:6-36.  scale_new is 3P floats. */
 int hlgs_compute_relocation(int P, const float* opacity_old, const float* scale_old, const int* N,
                             const float* binoms, int n_max, float* opacity_new, float* scale_new, void* stream);
+
+/* ---- MCMC densification (train_post.py:70-75, 707-789, 868-878) ---- */
+/* Counter-based random numbers (Philox4x32-10): number `index` of (seed, stream) depends on those three values only --
+ * no state, no dependence on the launch, the same on every rank.  counter = (index low, index high, stream, 0), key =
+ * (seed low, seed high); of the four output words w0..w3
+ *   HLGS_RNG_UNIFORM64: double u = ((w0 >> 5) * 2^26 + (w1 >> 6)) * 2^-53 in [0, 1);
+ *   HLGS_RNG_NORMAL32:  float  z = sqrtf(-2 logf(u1)) cosf(2 pi u2), u1 = ((w2 >> 8) + 1) 2^-24 in (0, 1],
+ *                       u2 = (w3 >> 8) 2^-24 (Box-Muller, cosine branch).
+ * hlgs_rng_fill writes numbers first_index .. first_index + n - 1 to out (device: n doubles or n floats);
+ * hlgs_rng_uniform_host writes the same uniforms to host memory and needs no device. */
+#define HLGS_RNG_UNIFORM64 0
+#define HLGS_RNG_NORMAL32 1
+int hlgs_rng_uniform_host(uint64_t seed, uint32_t stream, uint64_t first_index, int64_t n, double* out_host);
+int hlgs_rng_fill(int kind, uint64_t seed, uint32_t stream, uint64_t first_index, int64_t n, void* out, void* hip_stream);
+/* Opacity-weighted sampling with replacement.  Candidate i < n is storage row alive[i] (alive == NULL: row i) and
+ * weighs w_i = 1 / (1 + exp(-x_i)) in float64, x_i the float32 logit at opacity_base + alive[i] * stride_bytes
+ * (device memory or pinned host memory: the opacity word of packed host rows is read in place); logits below -103,
+ * where float32's sigmoid underflows, weigh exactly 0.  C = the inclusive prefix sum of w, accumulated in float64 in a
+ * fixed order.  Draw j < num takes uniform number j of (seed, stream_id) and selects the smallest i with
+ * C_i > u_j C_n, so a zero weight is never drawn; sampled[j] = alive[i] and counts (size int32, zeroed here) =
+ * bincount(sampled, minlength = size).  The reference's division by sum + eps (:1581) does not change the
+ * distribution and is not reproduced, and there is no 16,000,000-candidate subsampling (:1611-1613, :1709-1711).
+ * Bit-identical from run to run.  scratch: hlgs_mcmc_sample_scratch_size(n) bytes of device memory; its first
+ * 256-byte-aligned address holds HLGS_MCMC_HEADER_BYTES: double C_n, int32 status (bit 0: n == 0 or C_n is 0 or not
+ * finite -- nothing was drawn, sampled is -1; bit 1: a drawn row fell outside [0, size)), which the caller reads
+ * after the call (no host synchronisation here).  Rows alive[i] must lie inside the opacity storage. */
+#define HLGS_MCMC_HEADER_BYTES 16
+size_t hlgs_mcmc_sample_scratch_size(int64_t n);
+int hlgs_mcmc_sample(int64_t n, const void* opacity_base, int64_t stride_bytes, const int* alive, int64_t num,
+                     uint64_t seed, uint32_t stream_id, int* sampled, int* counts, int64_t size, void* scratch,
+                     void* hip_stream);
+/* The position noise of train_post.py:868-878 over rows first_row <= p < P, in place, one pass:
+ *   o = sigmoid(opacity_raw), s = exp(scaling_raw), q = normalize(rotation_raw) (normalised again as build_rotation
+ *   does), L = R(q) diag(s), w = 1 / (1 + exp(-100 ((1 - o) - 0.995))), means3D += L L^T (xi w scale),
+ * scale = MCMC_Noise_LR * xyz_lr; a row's arithmetic runs in float64 from the float32 inputs and the increment is
+ * rounded to float32 once.  xi = noise[3 p + c] (P x 3 floats) when noise is given, else normal number
+ * 3 p + c of (seed, stream = step).  The reference runs it after the optimizer step, on the updated parameters. */
+int hlgs_mcmc_noise(int64_t P, int64_t first_row, float* means3D, const float* opacity_raw, const float* scaling_raw,
+                    const float* rotation_raw, const float* noise, double scale, uint64_t seed, uint32_t step,
+                    void* hip_stream);
 
 /* Sparse Adam step of SparseGaussianAdam (alt_gaussian_rasterization/__init__.py:244-271, adam.cu:9-36):
  * for every element p of the N x M parameter whose Gaussian p / M is visible (visible: N bytes),

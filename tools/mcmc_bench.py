@@ -1,0 +1,158 @@
+"""Timings of the MCMC densification pieces on one GPU; not part of bench.py.
+
+  python tools/mcmc_bench.py noise   [--rows 600000]
+  python tools/mcmc_bench.py sample  [--n 16000000 --num 1600000 --host-n 50000000]
+  python tools/mcmc_bench.py round   [--leaves 1000000]
+
+Every figure is the median (min-max) of --reps calls after --warmup calls, timed with device events around a call
+that ends in a synchronise where the call itself does not.  One JSON line per measurement."""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for _p in (ROOT, os.path.join(ROOT, "hierarchical-lod-gaussians_amd"), os.path.join(ROOT, "tests")):
+    if _p not in sys.path:
+        sys.path.insert(0, _p)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+
+def timed(fn, warmup, reps):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        ms.append(a.elapsed_time(b))
+    ms.sort()
+    return dict(median_ms=round(ms[len(ms) // 2], 4), min_ms=round(ms[0], 4), max_ms=round(ms[-1], 4), reps=reps)
+
+
+def report(name, **kw):
+    print(json.dumps(dict(measurement=name, **kw)), flush=True)
+
+
+def bench_noise(a):
+    import mcmc_ref as R
+    from hlgs_core import mcmc
+    P = a.rows
+    g = torch.Generator().manual_seed(0)
+    op = (torch.randn(P, 1, generator=g) * 2).cuda()
+    sc = (torch.randn(P, 3, generator=g) * 0.5 - 2).cuda()
+    rot = torch.randn(P, 4, generator=g).cuda()
+    means = torch.zeros(P, 3, device="cuda")
+
+    def torch_step():
+        means.add_(R.noise_delta(op, sc, rot, torch.randn_like(means), 5e5, 1.6e-4, torch.float32))
+    report("noise_kernel", rows=P, bytes_per_row=56,
+           **timed(lambda: mcmc.position_noise_(means, op, sc, rot, 5e5, 1.6e-4, seed=1, step=3), a.warmup, a.reps))
+    report("noise_torch_composition", rows=P, **timed(torch_step, a.warmup, a.reps))
+
+
+def bench_sample(a):
+    from hlgs_core import mcmc
+    n, num = a.n, a.num
+    g = torch.Generator().manual_seed(0)
+    logits = torch.randn(n, 1, generator=g)
+    dev = logits.cuda()
+    report("sample_device", n=n, num=num, **timed(lambda: mcmc.sample_alive(dev, num, seed=1), a.warmup, a.reps))
+    nt = min(n, 2 ** 24)
+    probs = torch.sigmoid(dev[:nt, 0])
+    report("torch_multinomial", n=nt, num=num,
+           **timed(lambda: torch.bincount(torch.multinomial(probs, num, replacement=True), minlength=nt), a.warmup,
+                   a.reps))
+    del dev, probs, logits
+    # packed pinned rows (SPTCache.host: 192 floats per Gaussian, the opacity at word 6)
+    G = a.host_n
+    host = torch.zeros((G, 192), dtype=torch.float32, pin_memory=True)
+    host[:, 6] = torch.randn(G, generator=g)
+    op = host[:, 6:7]
+    report("sample_packed_host_rows_in_place", n=G, num=num, line_bytes_per_candidate=64,
+           **timed(lambda: mcmc.sample_alive(op, num, seed=1), 1, max(3, a.reps // 4)))
+
+    def copy_first():
+        mcmc.sample_alive(op.cuda(), num, seed=1)
+    report("sample_after_torch_copy_of_the_column", n=G, num=num, **timed(copy_first, 1, max(3, a.reps // 4)))
+    col = op.cuda()
+    report("sample_device_column_only", n=G, num=num,
+           **timed(lambda: mcmc.sample_alive(col, num, seed=1), 1, max(3, a.reps // 4)))
+
+
+def bench_round(a):
+    from hlgs_core import mcmc, spt
+    from hlgs_core import synthetic as S
+    from hlgs_core.spt_cache import NAMES, SPTCache
+    sky = 4
+    h = S.make_dynamic_hierarchy(S.make_gaussians(a.leaves, 0, S.make_camera(256, 192), seed=8), skybox_points=sky,
+                                 seed=8)
+    size = h["nodes"].shape[0]
+    cap = int(1.1 * size)
+    nodes = torch.zeros((cap, 6), dtype=torch.int32)
+    nodes[:size] = torch.tensor(h["nodes"])
+    shapes = dict(xyz=(3,), f_dc=(1, 3), opacity=(1,), scaling=(3,), rotation=(4,), f_rest=(15, 3))
+    storage = {k: torch.zeros((cap,) + shapes[k]) for k in NAMES}
+    storage["xyz"][:size] = torch.tensor(h["means3D"])
+    storage["scaling"][:size] = torch.log(torch.tensor(h["scales"]))
+    storage["rotation"][:size] = torch.tensor(h["rotations"])
+    op = torch.tensor(h["opacities"]).clamp(0.01, 0.99)
+    storage["opacity"][:size] = torch.log(op / (1 - op))
+    rng = np.random.default_rng(8)
+    leaves = torch.where(nodes[:size, 2] == 0)[0]
+    low = leaves[torch.tensor(rng.choice(len(leaves), size=len(leaves) // 20, replace=False))]
+    storage["opacity"][low] = float(np.log(0.001 / 0.999))
+    args = dict(SPT_Root_Volume=a.volume, target_granularity=a.granularity, min_SPT_Size=256)
+    b = spt.build_hierarchical_spt(nodes[:size], storage["xyz"][:size], storage["scaling"][:size], sky, *args.values())
+    cache = SPTCache(storage, b, sky)
+    cam = S.make_camera(320, 240, T=np.array([0.0, 0.0, 0.3]))
+    cache.step(cam["projmatrix"], cam["campos"])
+    resident = int(cache.render_indices.numel())
+
+    def clock():
+        torch.cuda.synchronize()
+        return time.perf_counter()
+    t = [clock()]
+    cache.reset()
+    t.append(clock())
+    dead = torch.where(cache.storage["opacity"][:size, 0] <= float(np.log(0.005 / 0.995)))[0]
+    new_size = mcmc.add_new_gs(cache.storage, nodes, size, 10 ** 9, seed=1)
+    t.append(clock())
+    mask = torch.zeros(new_size, dtype=torch.bool)
+    mask[dead] = True
+    mask &= nodes[:new_size, 2] == 0
+    moved = mcmc.relocate_gs(cache.storage, cache.opt_storage, nodes, mask, new_size, sky, seed=1)
+    t.append(clock())
+    b = spt.build_hierarchical_spt(nodes[:new_size], cache.storage["xyz"][:new_size],
+                                   cache.storage["scaling"][:new_size], sky, *args.values())
+    t.append(clock())
+    cache.reset(b)
+    t.append(clock())
+    names = ("reset", "spawn", "relocate", "spt_rebuild", "reset_with_spt")
+    report("densify_round", size=size, new_size=new_size, resident_rows=resident, relocated=moved, runs=1,
+           **{f"{k}_ms": round(1e3 * (y - x), 2) for k, x, y in zip(names, t, t[1:])})
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("what", choices=["noise", "sample", "round"])
+    ap.add_argument("--rows", type=int, default=600_000)
+    ap.add_argument("--n", type=int, default=16_000_000)
+    ap.add_argument("--num", type=int, default=1_600_000)
+    ap.add_argument("--host-n", type=int, default=50_000_000)
+    ap.add_argument("--leaves", type=int, default=1_000_000)
+    ap.add_argument("--volume", type=float, default=0.5)  # config #5 (bench.py): 0.5, 0.00228, 256
+    ap.add_argument("--granularity", type=float, default=0.00228)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--reps", type=int, default=20)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("mcmc_bench.py measures on the GPU; none is present")
+    {"noise": bench_noise, "sample": bench_sample, "round": bench_round}[a.what](a)
