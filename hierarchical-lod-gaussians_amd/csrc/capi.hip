@@ -743,6 +743,46 @@ int hlgs_knn_mean_dist2(int P, const float* xyz, void* scratch, float* out, void
     return check_stage(s, false, "knn");
 }
 
+// ---------------------------------------------------------------- hierarchy creation (hier_build.hip)
+size_t hlgs_hier_scratch_size(int N) { return hier_scratch_bytes(N); }
+
+static int hier_args(int N, int sh_floats, const HierIn& in)
+{
+    if (N < 1 || N > HLGS_HIER_MAX_N) return fail(HLGS_ERR_ARG, "N must be in [1, HLGS_HIER_MAX_N]");
+    if (sh_floats < 1) return fail(HLGS_ERR_ARG, "sh_floats < 1");
+    if (!in.xyz || !in.shs || !in.opacity || !in.scales || !in.rotations) return fail(HLGS_ERR_ARG, "missing tensor");
+    return HLGS_OK;
+}
+
+int hlgs_hier_valid_mask(int N, int sh_floats, const float* xyz, const float* shs, const float* opacity,
+                         const float* scales, const float* rotations, unsigned char* mask, void* stream)
+{
+    const HierIn in = {N, sh_floats, xyz, shs, opacity, scales, rotations};
+    if (int rc = hier_args(N, sh_floats, in)) return rc;
+    if (!mask) return fail(HLGS_ERR_ARG, "missing output");
+    hipStream_t s = (hipStream_t)stream;
+    hipGetLastError();
+    launch_hier_valid(in, 0, mask, nullptr, s);
+    return check_stage(s, false, "hier_valid_mask");
+}
+
+int hlgs_hier_build(int N, int sh_floats, const float* xyz, const float* shs, const float* opacity,
+                    const float* scales, const float* rotations, float* pos, float* out_shs, float* alpha,
+                    float* log_scales, float* rot, int* nodes, void* scratch, int stages, void* stream)
+{
+    const HierIn in = {N, sh_floats, xyz, shs, opacity, scales, rotations};
+    if (int rc = hier_args(N, sh_floats, in)) return rc;
+    if (!pos || !out_shs || !alpha || !log_scales || !rot || !nodes || !scratch)
+        return fail(HLGS_ERR_ARG, "missing output");
+    if ((uintptr_t)scratch % kAlign) return fail(HLGS_ERR_ARG, "scratch must be 256-byte aligned");
+    if (stages <= 0 || stages > HLGS_HIER_ALL) return fail(HLGS_ERR_ARG, "unknown stage");
+    const HierOut out = {pos, out_shs, alpha, log_scales, rot, nodes};
+    hipStream_t s = (hipStream_t)stream;
+    hipGetLastError();
+    launch_hier_build(in, out, scratch, stages, s);
+    return check_stage(s, false, "hier_build");
+}
+
 // ---------------------------------------------------------------- SPT streaming (stream.hip)
 size_t hlgs_upper_cut_scratch_size(int N)
 {

@@ -383,6 +383,29 @@ static_assert(kKnnBox == 64 && kKnnSuper == 64, "one lane per row of a box and p
 static_assert(kKnnSortTile % 256 == 0, "a sort tile is whole rounds of the histogram's 256 threads");
 size_t knn_scratch_bytes(int P);
 void launch_knn(int P, const float* xyz, void* scratch, float* out, hipStream_t s);
+// The sort of knn.hip on its own: P (key, value) pairs by the full 32-bit key, four stable LSD passes, so equal keys
+// keep the order they came in.  hist: radix_hist_elems(P) words, scan_tmp: scan_scratch_elems(radix_hist_elems(P)).
+// The result is in keys / vals; the *_tmp arrays are overwritten.
+size_t radix_hist_elems(size_t P);
+void radix_sort_pairs_u32(uint32_t P, uint32_t* keys, uint32_t* vals, uint32_t* keys_tmp, uint32_t* vals_tmp,
+                          uint32_t* hist, uint32_t* scan_tmp, hipStream_t s);
+
+// hier_build.hip: the dynamic hierarchy of N activated Gaussians (kd-tree, bottom-up merge, top-down rotation
+// alignment, pre-order node table).  A subtree of at most kHierCap leaves is finished by one workgroup.
+constexpr int kHierCap = HLGS_HIER_LDS_CAP;
+enum HierStage { HB_KD_TOP = 0, HB_KD_LDS, HB_LEAVES, HB_MERGE, HB_ALIGN, HB_FINISH, HB_STAGES };
+struct HierIn {
+    int N, shf;
+    const float *xyz, *shs, *opacity, *scales, *rotations;
+};
+struct HierOut {
+    float *pos, *shs, *alpha, *log_scales, *rot;
+    int* nodes;
+};
+size_t hier_scratch_bytes(int N);
+void launch_hier_valid(const HierIn& in, int strict, uint8_t* mask, uint32_t* status, hipStream_t s);
+// stages: bit i runs HierStage i (HLGS_HIER_ALL: the build; single bits in order: the same build, stage by stage)
+void launch_hier_build(const HierIn& in, const HierOut& out, void* scratch, int stages, hipStream_t s);
 
 // mcmc.hip: opacity-weighted sampling, the position noise and the counter-based numbers of the densification round
 constexpr int kMcmcItems = 2048;  // candidates per block of the sampler's float64 prefix sum (256 threads x 8)

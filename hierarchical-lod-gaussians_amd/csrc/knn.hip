@@ -420,27 +420,37 @@ size_t knn_scratch_bytes(int P)
     return total;
 }
 
+// The sort on its own (also used by hier_build.hip): P pairs by the whole 32-bit key, stable.
+size_t radix_hist_elems(size_t P) { return (size_t)kRadix * knn_tiles(P); }
+
+void radix_sort_pairs_u32(uint32_t P, uint32_t* keys, uint32_t* vals, uint32_t* keys_tmp, uint32_t* vals_tmp,
+                          uint32_t* hist, uint32_t* scan_tmp, hipStream_t s)
+{
+    const uint32_t tiles = (uint32_t)knn_tiles(P);
+    uint32_t *kin = keys, *vin = vals, *kout = keys_tmp, *vout = vals_tmp;
+    const size_t nh = (size_t)kRadix * tiles;
+    for (int shift = 0; shift < 32; shift += kRadixBits) {  // four passes, ending in keys / vals
+        hipLaunchKernelGGL(k_knn_hist, dim3(tiles), dim3(256), 0, s, P, kin, shift, tiles, hist);
+        scan_inclusive_u32(hist, hist, nh, scan_tmp, s);
+        hipLaunchKernelGGL(k_knn_scatter, dim3(tiles), dim3(64), 0, s, P, kin, vin, shift, tiles, hist, kout, vout);
+        uint32_t* t = kin;
+        kin = kout, kout = t;
+        t = vin, vin = vout, vout = t;
+    }
+}
+
 void launch_knn(int P_, const float* xyz, void* scratch, float* out, hipStream_t s)
 {
     if (P_ <= 0) return;
     const uint32_t P = (uint32_t)P_;
     const KnnBufs b = carve_knn(scratch, P, nullptr);
-    const uint32_t tiles = (uint32_t)knn_tiles(P), nb = (uint32_t)knn_boxes(P), ns = (uint32_t)knn_supers(P);
+    const uint32_t nb = (uint32_t)knn_boxes(P), ns = (uint32_t)knn_supers(P);
     const uint32_t per256 = (P + 255u) / 256u;
     const int nparts = (int)(per256 < (uint32_t)kBoxParts ? per256 : (uint32_t)kBoxParts);
     hipLaunchKernelGGL(k_knn_bbox, dim3(nparts), dim3(256), 0, s, P, xyz, b.parts);
     hipLaunchKernelGGL(k_knn_keys, dim3(per256), dim3(256), 0, s, P, xyz, b.parts, nparts, b.keys_a, b.idx_a);
-    uint32_t *kin = b.keys_a, *vin = b.idx_a, *kout = b.keys_b, *vout = b.idx_b;
-    const size_t nh = (size_t)kRadix * tiles;
-    for (int shift = 0; shift < 32; shift += kRadixBits) {  // 30 key bits: four passes, ending in keys_a / idx_a
-        hipLaunchKernelGGL(k_knn_hist, dim3(tiles), dim3(256), 0, s, P, kin, shift, tiles, b.hist);
-        scan_inclusive_u32(b.hist, b.hist, nh, b.scan_tmp, s);
-        hipLaunchKernelGGL(k_knn_scatter, dim3(tiles), dim3(64), 0, s, P, kin, vin, shift, tiles, b.hist, kout, vout);
-        uint32_t* t = kin;
-        kin = kout, kout = t;
-        t = vin, vin = vout, vout = t;
-    }
-    hipLaunchKernelGGL(k_knn_rows, dim3((nb + 3u) / 4u), dim3(256), 0, s, P, nb, xyz, vin, b.rows, b.blo, b.bhi);
+    radix_sort_pairs_u32(P, b.keys_a, b.idx_a, b.keys_b, b.idx_b, b.hist, b.scan_tmp, s);  // 30 key bits
+    hipLaunchKernelGGL(k_knn_rows, dim3((nb + 3u) / 4u), dim3(256), 0, s, P, nb, xyz, b.idx_a, b.rows, b.blo, b.bhi);
     hipLaunchKernelGGL(k_knn_supers, dim3((ns + 3u) / 4u), dim3(256), 0, s, nb, ns, b.blo, b.bhi, b.slo, b.shi);
     hipLaunchKernelGGL(k_knn_search, dim3(nb), dim3(64), 0, s, P, nb, ns, b.rows, b.blo, b.bhi, b.slo, b.shi, out);
 }

@@ -1,7 +1,9 @@
 """Drop-in `gaussian_hierarchy` for MI355X: every function of `gaussian_hierarchy._C`
 (submodules/gaussianhierarchy/ext.cpp:15-27: file I/O, traversal, runtime LOD cuts, Morton codes) plus
 `interpolate_lod`, a HIP replacement for the
-child/parent lerp `render_post` performs in Python (gaussian_renderer/__init__.py:304-339).
+child/parent lerp `render_post` performs in Python (gaussian_renderer/__init__.py:304-339), and
+`create_dynamic_hierarchy`, the offline GaussianHierarchyCreator (mainHierarchyCreator.cpp) on the GPU
+(hlgs_core.hierarchy.build_dynamic_hierarchy).
 """
 import torch
 
@@ -9,10 +11,13 @@ from . import _C
 from ._C import (expand_to_size, expand_to_size_dynamic, expand_to_target, get_interpolation_weights,  # noqa: F401
                  get_interpolation_weights_dynamic, get_morton_indices, get_spt_cut_cuda, load_dynamic_hierarchy,
                  load_hierarchy, write_dynamic_hierarchy, write_hierarchy)
+from hlgs_core.hierarchy import build_dynamic_hierarchy as create_dynamic_hierarchy  # noqa: F401
+from hlgs_core.hierarchy import valid_gaussian_mask  # noqa: F401
 
-__all__ = ["_C", "expand_to_size", "expand_to_size_dynamic", "expand_to_target", "get_interpolation_weights",
-           "get_interpolation_weights_dynamic", "get_morton_indices", "get_spt_cut_cuda", "interpolate_lod",
-           "load_dynamic_hierarchy", "load_hierarchy", "write_dynamic_hierarchy", "write_hierarchy"]
+__all__ = ["_C", "create_dynamic_hierarchy", "expand_to_size", "expand_to_size_dynamic", "expand_to_target",
+           "get_interpolation_weights", "get_interpolation_weights_dynamic", "get_morton_indices", "get_spt_cut_cuda",
+           "interpolate_lod", "load_dynamic_hierarchy", "load_hierarchy", "valid_gaussian_mask",
+           "write_dynamic_hierarchy", "write_hierarchy"]
 
 
 class _InterpolateLOD(torch.autograd.Function):

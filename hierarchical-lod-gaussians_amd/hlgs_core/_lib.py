@@ -99,6 +99,9 @@ _SIGS = {
     "hlgs_morton_codes": (_i, [_i, _vp, _vp, _vp, _vp, _vp]),
     "hlgs_knn_scratch_size": (_sz, [_i]),
     "hlgs_knn_mean_dist2": (_i, [_i, _vp, _vp, _vp, _vp]),
+    "hlgs_hier_scratch_size": (_sz, [_i]),
+    "hlgs_hier_valid_mask": (_i, [_i, _i] + [_vp] * 7),
+    "hlgs_hier_build": (_i, [_i, _i] + [_vp] * 12 + [_i, _vp]),
     "hlgs_upper_cut_scratch_size": (_sz, [_i]),
     "hlgs_upper_tree_cut": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _i, _vp, _vp, C.POINTER(_i), _vp]),
     "hlgs_upper_tree_cut_device": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _i, _vp, _vp, _vp, _vp]),

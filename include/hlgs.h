@@ -316,6 +316,56 @@ int hlgs_morton_codes(int P, const float* xyz, const float* mn, const float* mx,
 size_t hlgs_knn_scratch_size(int P);
 int hlgs_knn_mean_dist2(int P, const float* xyz, void* scratch, float* out, void* stream);
 
+/* ---- The dynamic hierarchy of N flat Gaussians (the offline GaussianHierarchyCreator, on the device) ----
+ * Inputs are activated Gaussians as submodules/gaussianhierarchy/loader.cpp:54-72 leaves them, device float32:
+ * xyz N x 3, shs N x sh_floats (any order; rows are only copied and blended), opacity N in (0, 1], scales N x 3
+ * (exp of the stored ones), rotations N x 4 (w, x, y, z; normalised inside as loader.cpp:56 does).  N in
+ * [1, HLGS_HIER_MAX_N] (2N - 1 node ids are int32) and sh_floats >= 1, else HLGS_ERR_ARG.  Nothing is allocated and
+ * nothing is read back; every launch goes to `stream`.
+ *
+ * hlgs_hier_valid_mask: mask[i] = 1 iff the creator keeps row i (mainHierarchyCreator.cpp:87-152): opacity neither
+ *   inf, NaN nor 0, no scale above 10, no NaN in scale, rotation, position or SH.
+ *
+ * hlgs_hier_build writes the 2N - 1 pre-order rows (row id == node id) of
+ *   PointbasedKdTreeGenerator.cpp:16-68  bounds over position -+ 3 max(scale), the first axis of the strictly greatest
+ *       extent, the num / 2 members of smallest position[axis] to the left; ties (which nth_element leaves open) by
+ *       (position[axis] compared as floats, input row);
+ *   ClusterMerger.cpp:23-141  bottom-up, float32 in the reference's order: w_i = opacity_i ((s0 s1 + s0 s2) + s1 s2),
+ *       a_i = w_i / (w0 + w1), position and SH row 0 + a0 x0 + a1 x1, cov = sum a_i (cov_i + d_i d_i^T) over the
+ *       children's accumulated covariances; eigenvalues ascending (3 x 3 cyclic Jacobi in float64), diagonal bumped by
+ *       max(1e-4 m_ii, FLT_EPSILON) while one is exactly 0 (at most 16 times), third eigenvector negated in a
+ *       left-handed frame, scale = sqrt|lambda|, rotation = Eigen's quaternion of the eigenvectors, opacity =
+ *       (w0 + w1) / surface(scale), not clamped; the root is merged too;
+ *   rotation_aligner.cpp:23-115  top-down: every child takes the first of its 24 proper signed axis permutations, in
+ *       the loop order (i, j, k, state), whose Frobenius product with the parent's rotation is strictly the greatest
+ *       above 0, and its scales are permuted alike; a child with no such candidate is left unchanged;
+ *   writer.cpp:99-204  nodes (2N - 1) x 6 int32 {depth, parent (-1 for the root), child_count (2 or 0), first_child
+ *       (id + 1 for every node), next_sibling (the right sibling's id for a left child, else 0), max_side_length (the
+ *       input row of a leaf, -1 for merged nodes)}; log_scales = log(scale); alpha as is.
+ * pos (2N-1) x 3, shs (2N-1) x sh_floats, alpha 2N-1, log_scales (2N-1) x 3, rot (2N-1) x 4 device float32.
+ * Results do not change from run to run.  Every memory index stays in range for any input bits.
+ * scratch: hlgs_hier_scratch_size(N) bytes of device memory, 256-byte aligned.  Its first word is the status, valid
+ * once the stream has passed the call: the caller reads it (the build's one read-back) and treats a non-zero value as
+ * an error: HLGS_HIER_STATUS_INVALID a row holds a non-finite value or has opacity 0; _NAN an eigenvalue was NaN (the
+ * reference throws); _BUMP an eigenvalue was still 0 after 16 bumps (the reference would go on).
+ * A subtree of at most HLGS_HIER_LDS_CAP leaves is finished by one workgroup (its kd levels in LDS, its merge and
+ * alignment levels behind barriers); the levels above are one group of launches each.
+ * stages: HLGS_HIER_ALL.  For measurement the stages can be run one call each, in order (bit 0 kd top levels, 1 kd in
+ * LDS, 2 leaf rows and node table, 3 merge, 4 align, 5 log of the scales); the state between them is in scratch and
+ * the outputs. */
+#define HLGS_HIER_LDS_CAP 2048
+#define HLGS_HIER_MAX_N (1 << 30)
+#define HLGS_HIER_ALL 0x3f
+#define HLGS_HIER_STATUS_INVALID 1u
+#define HLGS_HIER_STATUS_NAN 2u
+#define HLGS_HIER_STATUS_BUMP 4u
+size_t hlgs_hier_scratch_size(int N);
+int hlgs_hier_valid_mask(int N, int sh_floats, const float* xyz, const float* shs, const float* opacity,
+                         const float* scales, const float* rotations, unsigned char* mask, void* stream);
+int hlgs_hier_build(int N, int sh_floats, const float* xyz, const float* shs, const float* opacity,
+                    const float* scales, const float* rotations, float* pos, float* out_shs, float* alpha,
+                    float* log_scales, float* rot, int* nodes, void* scratch, int stages, void* stream);
+
 /* ---- SPT streaming around the SPT cut (train_post.py:323-491) ---- */
 /* Coarse cut of the upper tree (GaussianModel.cut_hierarchy_on_condition with root 0, no upper-tree output,
  * leave_out_of_cut_condition = frustum_cull_spheres: scene/gaussian_model.py:364-404, 67-100, as train_post.py

@@ -15,6 +15,10 @@
   knn       simple_knn.distCUDA2 (create_from_pcd's initial scales) at 250k, 1M and 4M points on a uniform cube and
             on a Gaussian cloud with a 10% skybox shell at 10x its radius, the scenes alternated from round to round;
             beside them the all-pairs torch restatement (tests/knn_ref.py) at 250k, timed once.
+  hier_build  hlgs_core.hierarchy.build_dynamic_hierarchy (the offline GaussianHierarchyCreator on the GPU) over
+            250k, 1M and 4M synthetic leaves with 48 SH floats: the whole build and every stage on its own (event
+            times; the stages are then one call each); beside them the wall time of the recursive numpy restatement
+            (tests/hier_build_ref.py) at 20,000 leaves and of synthetic.make_dynamic_hierarchy at 1M.
   stream    train_post.py's SPT cache over the same hierarchy: SPT construction (host code), then a camera path
             of views through SPTCache.step (coarse cut, cache bookkeeping, SPT cut, write-back and load of the
             six parameters and twelve Adam moments to and from pinned host storage) and the dense Adam step of
@@ -302,6 +306,49 @@ def bench_knn(sizes=(250_000, 1_000_000, 4_000_000), rounds=5, calls=4, restatem
     return out
 
 
+def bench_hier_build(sizes=(250_000, 1_000_000, 4_000_000), restatement_P=20_000, numpy_builder_P=1_000_000):
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import hier_build_ref as HR
+    from hlgs_core import hierarchy as H
+    cam = S.make_camera(1920, 1080)
+    out = dict(lds_cap=H.LDS_CAP)
+
+    def inputs(P):
+        g = S.make_gaussians(P, 3, cam, seed=0)
+        return g, [torch.tensor(g[k], device=DEV) for k in ("means3D", "shs", "opacities", "scales", "rotations")]
+
+    for P in sizes:
+        print(f"hier_build: {P} leaves", file=sys.stderr, flush=True)
+        _, dev = inputs(P)
+        whole = timed(lambda: H.build_dynamic_hierarchy(*dev), iters=5, warmup=1)
+        stages = []
+        for _ in range(3):
+            ms = {}
+            H.build_dynamic_hierarchy(*dev, stage_ms=ms)
+            stages.append(ms)
+        out[str(P)] = dict(workload=f"{P} leaves, 48 SH floats, {2 * P - 1} rows out", build_ms=round(whole, 3),
+                           leaves_per_s=round(P / (whole * 1e-3)),
+                           stage_ms={k: round(float(np.median([m[k] for m in stages])), 3) for k in H.STAGES})
+        del dev
+    g, dev = inputs(restatement_P)
+    sc = dict(xyz=g["means3D"], shs=g["shs"].reshape(restatement_P, -1), opacity=g["opacities"].reshape(-1),
+              scales=g["scales"], rotations=g["rotations"])
+    t0 = time.perf_counter()
+    ref = HR.build_ref(sc, np.float32)
+    ref_s = time.perf_counter() - t0
+    nodes = H.build_dynamic_hierarchy(*dev)[5].cpu().numpy()
+    out["restatement"] = dict(workload=f"recursive numpy restatement, float32, {restatement_P} leaves, one run",
+                              s=round(ref_s, 2), gpu_ms=round(timed(lambda: H.build_dynamic_hierarchy(*dev), 5, 1), 3),
+                              nodes_equal=bool((nodes == ref["nodes"]).all()))
+    g = S.make_gaussians(numpy_builder_P, 3, cam, seed=0)
+    t0 = time.perf_counter()
+    S.make_dynamic_hierarchy(g, seed=0)
+    out["make_dynamic_hierarchy"] = dict(workload=f"synthetic.make_dynamic_hierarchy (numpy, Morton pairs), "
+                                                  f"{numpy_builder_P} leaves, one run",
+                                         s=round(time.perf_counter() - t0, 2))
+    return out
+
+
 def bench_stream(P, views=12):
     from hlgs_core import spt
     from hlgs_core.spt_cache import NAMES, SPTCache
@@ -378,6 +425,8 @@ def main():
         out["morton"] = bench_morton(xyz)
     if "knn" in only:
         out["knn"] = bench_knn(tuple(int(v) for v in args.knn_sizes.split(",")))
+    if "hier_build" in only:
+        out["hier_build"] = bench_hier_build()
     if "stream" in only:
         out["stream"] = bench_stream(args.P)
     print(json.dumps(out))
