@@ -166,14 +166,28 @@ def test_colour_factored_sh_exchange_partial_degree(alt):
     _colour_factored_case(alt, False, 1)
 
 
-def _colour_factored_case(alt, overlap, D):
-    """D: the active SH degree of both the rasterizer settings and the rebuild; the scene stores 16 rows."""
+@pytest.mark.gpu
+@pytest.mark.parametrize("alt,D", [(False, 3), (True, 3), (False, 1), (True, 1)])
+def test_colour_factored_sh_exchange_with_clamped_channels(alt, D):
+    """The same exchange on the frustum-clamp scene (tests/clamp_scenes.py), where a third of the colour channels clamp
+    at 0 instead of two in ten thousand: the plain backward it is compared with zeroes those channels' rows, and so
+    must the rebuild, per view -- the two cameras differ, so some channels clamp in one view only."""
+    _colour_factored_case(alt, False, D, scene="frustum")
+
+
+def _colour_factored_case(alt, overlap, D, scene="plain"):
+    """D: the active SH degree of both the rasterizer settings and the rebuild; the scene stores 16 rows.
+    scene: clamp_scenes.two_view_scene's kind."""
     import ctypes as C
+    import clamp_scenes as CS
     from hlgs_core import _lib as L
     from hlgs_core.dp import FlatGradExchange
     W, H = 160, 96
-    cams = [S.make_camera(W, H), S.make_camera(W, H, T=np.array([0.3, -0.1, 0.2]))]
-    sc = S.make_gaussians(6000, 3, cams[0], seed=7)
+    sc, cams = CS.two_view_scene(scene, W, H)
+    if scene == "frustum":  # channels clamped in one view only (55 at D = 3, 11 at D = 1) and in both (~2,700)
+        a, b, seen = CS.clamp_bits_of_two_views(sc, cams, D)
+        bits = lambda m: int(np.unpackbits(m[seen]).sum())  # noqa: E731
+        assert bits(a ^ b) >= 5 and bits(a & b) >= 1000, (bits(a ^ b), bits(a & b))
     g, gd = S.upstream_grads(W, H, seed=8)
     t = lambda a: torch.tensor(np.ascontiguousarray(a), device="cuda", requires_grad=True)  # noqa: E731
     gc, gi = torch.tensor(g, device="cuda"), torch.tensor(gd, device="cuda")
@@ -214,6 +228,13 @@ def _colour_factored_case(alt, overlap, D):
     for cam in cams:
         backward(cam)
         plain.append([p.grad.clone() for p in params])
+    if scene == "frustum":  # the plain backward zeroes exactly the channels the oracle clamps, view by view
+        for mask, pl in zip((a, b), plain):
+            for c in range(3):
+                on = torch.tensor(((mask >> c) & 1) != 0, device="cuda")
+                for grad in pl[4:]:
+                    assert torch.all(grad[on][:, :, c] == 0)
+                assert torch.count_nonzero(pl[4][~on][:, 0, c]) > 100
     ex = FlatGradExchange(params, colour_factor=factor, overlap=overlap)
     rows = []
     try:

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 import torch
 
+import clamp_scenes as CS
 from hlgs_core import synthetic as S
 from oracle import oracle as O
 
@@ -93,7 +94,8 @@ class _AAScale(torch.autograd.Function):
     """h = sqrt(max(2.5e-5, det(cov)/det(cov + 0.3 I))) with the reference's backward
     (backward.cu:212-246).  Quirk: that backward evaluates d(ratio)/d(cov), derived for the undilated
     covariance, at the *dilated* entries (c_xx, c_yy already include +0.3), so it is not the exact
-    derivative of its own forward.  Every other term of this restatement is plain autograd."""
+    derivative of its own forward.  The other modelled departures are _frustum_clamp and, for the alt rasterizer,
+    _ClampST; every other term of this restatement is plain autograd."""
 
     @staticmethod
     def forward(ctx, a, b, c):
@@ -126,11 +128,26 @@ class _ClampST(torch.autograd.Function):
         return g
 
 
-def torch_render(sc, cam, fr, deg, alt=False, aa=True, scale_modifier=1.0):
+def _frustum_clamp(x, z, lim, quirk=True):
+    """t.x (or t.y) of the EWA Jacobian: clamp(x / z, -lim, lim) * z (forward.cu:141-176) with the reference's backward
+    (backward.cu:185-186, 310-312; DESIGN A-38).  Quirk: once x / z is outside +-lim, that backward treats the clamped
+    t.x as a constant -- dL/dt.x is multiplied by x_grad_mul = 0, and dL/dt.z gets 2 fx t.x / t.z^3 dL/dJ02 with the
+    clamped t.x, the derivative of J02 = -fx t.x / t.z^2 at fixed t.x.  The exact derivative of clamp(x / z) * z would
+    have t.x = +-lim z move with z.  Modelled by detaching the clamped value; the identity (x itself, full gradient)
+    for an unclamped row.  quirk=False: plain autograd of the forward, for the negative control only."""
+    r = x / z
+    c = torch.clamp(r, -lim, lim) * z
+    if not quirk:
+        return c
+    return torch.where(r.abs() > lim, c.detach(), x)
+
+
+def torch_render(sc, cam, fr, deg, alt=False, aa=True, scale_modifier=1.0, clamp_quirk=True):
     """Differentiable float64 forward with the reference's semantics; the per-tile sorted lists come from
     the oracle frame (the sort itself has no gradient).  alt=True: the alt rasterizer's forward (AA scaling
     only when `aa`) with its backward's two departures from autograd modelled explicitly -- the clamp
     gradient passes through, and the T_final * bg term enters dL/dalpha twice (backward.cu:608, 619).
+    clamp_quirk: _frustum_clamp's model of the backward outside 1.3x the frustum (False: the negative control).
 
     scale_modifier: the covariance is built from the effective scale eff = scale_modifier * scales, returned as
     out["eff"] with its gradient retained (the reference's dL_dscale is the gradient of eff, DESIGN A-23).
@@ -171,8 +188,8 @@ def torch_render(sc, cam, fr, deg, alt=False, aa=True, scale_modifier=1.0):
     A = view[:3, :3].T  # linear part of the view transform acting on column vectors
     tz = tview[:, 2]
     limx, limy = 1.3 * cam["tanfovx"], 1.3 * cam["tanfovy"]
-    tx = torch.clamp(tview[:, 0] / tz, -limx, limx) * tz
-    ty = torch.clamp(tview[:, 1] / tz, -limy, limy) * tz
+    tx = _frustum_clamp(tview[:, 0], tz, limx, clamp_quirk)
+    ty = _frustum_clamp(tview[:, 1], tz, limy, clamp_quirk)
     zero = torch.zeros_like(tz)
     J = torch.stack([torch.stack([fx / tz, zero, -fx * tx / (tz * tz)], -1),
                      torch.stack([zero, fy / tz, -fy * ty / (tz * tz)], -1)], -2)
@@ -262,11 +279,14 @@ def test_oracle_matches_float64_autograd(P, deg, W, H, bg, realcam):
     else:
         cam = real_camera_small(realcam, W, H, bg=bg, **(dict(primx=0.47, primy=0.53) if realcam == 9 else {}))
     sc = S.make_gaussians(P, deg, cam, seed=P)
+    _hierarchy_case(sc, cam, deg, 1e-5 if realcam is None else _fwd_tol_far(cam, sc))
+
+
+def _hierarchy_case(sc, cam, deg, tol):
     fr = O.forward(sc, S.cam_numpy(cam))
-    g, gd = S.upstream_grads(W, H)
+    g, gd = S.upstream_grads(cam["W"], cam["H"])
     gr = O.backward(fr, sc, g, gd)
     tr = torch_render(sc, cam, fr, deg)
-    tol = 1e-5 if realcam is None else _fwd_tol_far(cam, sc)
     assert _rel(fr.color, tr["color"].detach().numpy()) < tol
     assert _rel(fr.invdepth, tr["invdepth"].detach().numpy()) < tol
     loss = (tr["color"] * torch.tensor(g, dtype=torch.float64)).sum() + \
@@ -283,6 +303,71 @@ def test_oracle_matches_float64_autograd(P, deg, W, H, bg, realcam):
     # invisible Gaussians receive exactly zero
     for name in ("dmean3D", "dscale", "drot", "dopacity", "dsh"):
         assert np.all(gr[name][~vis] == 0)
+    return fr, gr, tr
+
+
+# ---- the clamp scenes (tests/clamp_scenes.py): contributing Gaussians outside 1.3x the frustum, a third of the colour
+#      channels clamped, splats on the anti-aliasing floor, quaternions used unnormalised
+
+def _clamp_cam(realcam, W, H, bg):
+    return S.make_camera(W, H, bg=bg) if realcam is None else real_camera_small(realcam, W, H, bg=bg)
+
+
+def _clamp_scene(kind, P, deg, W, H, realcam, bg):
+    """kind: "frustum", "frustum-q" (unnormalised quaternions), "plain-q" (make_gaussians with unnormalised
+    quaternions) or "aa" (the anti-aliasing floor scene, synthetic camera)."""
+    if kind == "aa":
+        sc, cam = CS.aa_floor_scene(P, W, H, seed=P, deg=deg)
+        cam = S.make_camera(W, H, bg=bg)  # the same pose with this case's background
+    elif kind == "plain-q":
+        cam = _clamp_cam(realcam, W, H, bg)
+        sc = CS.unnormalise_quaternions(S.make_gaussians(P, deg, cam, seed=P), seed=P)
+    else:
+        sc, cam = CS.frustum_clamp_scene(P, deg, W, H, seed=P, cam=_clamp_cam(realcam, W, H, bg),
+                                         unnormalised=kind == "frustum-q")
+    return sc, cam
+
+
+def _assert_clamped_rows(kind, sc, cam, fr, gr, tr):
+    """The sharp part of a clamp-scene case: dmean3D over the clamped contributing rows alone, under the bound of the
+    whole tensor, so that a fault there cannot hide behind larger unclamped rows; and what the case is there for
+    really happens in it."""
+    contrib = gr["dopacity"][:, 0] != 0
+    if kind.startswith("frustum"):
+        xc, yc = CS.clamp_classes(sc, cam)
+        for rows in (xc & ~yc & contrib, yc & ~xc & contrib, xc & yc & contrib):
+            assert rows.sum() >= 10
+            e = _rel(gr["dmean3D"][rows], tr["means"].grad.numpy()[rows])
+            assert e < 2e-3, f"dmean3D over {rows.sum()} clamped contributing rows: {e}"
+        assert min(int((((fr.clamped >> c) & 1) != 0)[contrib].sum()) for c in range(3)) >= 10
+    if kind == "aa":
+        floor = np.arange(len(contrib)) < len(contrib) // 2
+        assert contrib[floor].all()
+        e = _rel(gr["dopacity"][floor], tr["opac"].grad.numpy()[floor])
+        assert e < 2e-3, f"dopacity over the floor rows: {e}"
+    if kind.endswith("-q"):
+        assert np.median(np.abs(np.linalg.norm(sc["rotations"], axis=1) - 1)) > 0.1
+
+
+CLAMP_CASES = [("frustum", 300, 3, 64, 48, (0.0, 0.0, 0.0), None),
+               ("frustum", 300, 2, 60, 44, (0.3, 0.2, 0.1), 5),
+               ("frustum-q", 300, 1, 64, 48, (0.2, 0.5, 0.8), None),
+               ("frustum-q", 300, 3, 60, 44, (0.0, 0.0, 0.0), 5),
+               ("plain-q", 300, 2, 64, 48, (0.1, 0.1, 0.1), 5),
+               ("aa", 300, 1, 64, 48, (0.3, 0.2, 0.1), None)]
+
+
+@pytest.mark.parametrize("kind,P,deg,W,H,bg,realcam", CLAMP_CASES)
+def test_oracle_matches_float64_autograd_on_clamp_scenes(kind, P, deg, W, H, bg, realcam):
+    """test_oracle_matches_float64_autograd's comparison, same bounds, on the scenes of tests/clamp_scenes.py.
+    Measured: colour <= 8e-7 and inverse depth <= 1.6e-6 of the image's maximum, every gradient <= 7.1e-6 (drot with
+    unnormalised quaternions), dmean3D over the clamped rows <= 1.9e-6, dopacity over the floor rows 2.4e-7.
+    Without the clamp model of _frustum_clamp (plain autograd of clamp(x / z) * z) the first case's dmean3D is off by
+    1.3e-1 of the tensor's maximum, and so is an oracle whose x_grad_mul is always 1 (1.2e-1): the reference's
+    backward is not the derivative of its forward there, and the comparison sees either side getting it wrong."""
+    sc, cam = _clamp_scene(kind, P, deg, W, H, realcam, bg)
+    fr, gr, tr = _hierarchy_case(sc, cam, deg, 1e-5 if realcam is None else _fwd_tol_far(cam, sc))
+    _assert_clamped_rows(kind, sc, cam, fr, gr, tr)
 
 
 def test_oracle_zero_instances_and_empty():
@@ -327,12 +412,16 @@ def test_alt_oracle_matches_float64_autograd(P, deg, W, H, bg, aa, realcam):
     cam = S.make_camera(W, H, bg=bg) if realcam is None else real_camera_small(realcam, W, H, bg=bg)
     sc = alt_scene(S.make_gaussians(P, deg, cam, seed=P + 7), aa)
     sc["opacities"][: P // 10] = 0.999  # some splats reach the 0.99 clamp
+    _alt_case(sc, cam, deg, aa, 1e-5 if realcam is None else _fwd_tol_far(cam, sc))
+
+
+def _alt_case(sc, cam, deg, aa, tol):
+    W, H = cam["W"], cam["H"]
     fr = O.forward(sc, S.cam_numpy(cam))
     assert fr.invdepth.shape == (1, H, W)
     g, gd = S.upstream_grads(W, H)
     gr = O.backward(fr, sc, g, gd)
     tr = torch_render(sc, cam, fr, deg, alt=True, aa=aa)
-    tol = 1e-5 if realcam is None else _fwd_tol_far(cam, sc)
     assert _rel(fr.color, tr["color"].detach().numpy()) < tol
     assert _rel(fr.invdepth, tr["invdepth"].detach().numpy()) < tol
     loss = (tr["color"] * torch.tensor(g, dtype=torch.float64)).sum() + \
@@ -346,6 +435,25 @@ def test_alt_oracle_matches_float64_autograd(P, deg, W, H, bg, aa, realcam):
         assert e < 2e-3, f"{name}: alt oracle vs autograd rel err {e}"
     e = _rel(gr["dmean2D"][vis, :2], tr["ndc"].grad.numpy()[vis])
     assert e < 2e-3, f"dmean2D: {e}"
+    return fr, gr, tr
+
+
+@pytest.mark.parametrize("kind,P,deg,W,H,bg,aa,realcam", [("frustum", 300, 3, 64, 48, (0.2, 0.4, 0.6), True, None),
+                                                          ("frustum", 300, 2, 60, 44, (0.0, 0.0, 0.0), False, 5),
+                                                          ("frustum-q", 300, 1, 60, 44, (0.3, 0.1, 0.6), True, 5),
+                                                          ("plain-q", 300, 2, 64, 48, (0.0, 0.0, 0.0), False, None),
+                                                          ("aa", 300, 1, 64, 48, (0.2, 0.5, 0.8), True, None)])
+def test_alt_oracle_matches_float64_autograd_on_clamp_scenes(kind, P, deg, W, H, bg, aa, realcam):
+    """test_alt_oracle_matches_float64_autograd's comparison, same bounds, on the scenes of tests/clamp_scenes.py
+    (antialiasing on and off; the floor scene with it on, where the floor exists).  Measured: forward <= 1.6e-6, every
+    gradient <= 5.3e-6, dmean3D over the clamped rows <= 1.2e-6."""
+    sc, cam = _clamp_scene(kind, P, deg, W, H, realcam, bg)
+    sc = alt_scene(sc, aa)
+    if kind != "aa":  # the floor rows' opacity range is part of that scene
+        sc["opacities"] = sc["opacities"].copy()
+        sc["opacities"][: P // 10] = 0.999
+    fr, gr, tr = _alt_case(sc, cam, deg, aa, 1e-5 if realcam is None else _fwd_tol_far(cam, sc))
+    _assert_clamped_rows(kind, sc, cam, fr, gr, tr)
 
 
 @pytest.mark.parametrize("alt,aa,mod,rows_deg,D,realcam,W,H,bg", [
@@ -375,11 +483,15 @@ def test_oracle_scale_modifier_and_partial_degree(alt, aa, mod, rows_deg, D, rea
     if alt:
         sc = alt_scene(sc, aa)
         sc["opacities"][: P // 10] = 0.999
+    _modifier_case(sc, cam, alt, aa, mod, rows_deg, D, _fwd_tol_far(cam, sc))
+
+
+def _modifier_case(sc, cam, alt, aa, mod, rows_deg, D, tol):
+    P, W, H = sc["means3D"].shape[0], cam["W"], cam["H"]
     fr = O.forward(sc, S.cam_numpy(cam))
     g, gd = S.upstream_grads(W, H)
     gr = O.backward(fr, sc, g, gd)
     tr = torch_render(sc, cam, fr, D, alt=alt, aa=aa, scale_modifier=mod)
-    tol = _fwd_tol_far(cam, sc)
     assert _rel(fr.color, tr["color"].detach().numpy()) < tol
     assert _rel(fr.invdepth, tr["invdepth"].detach().numpy()) < tol
     loss = (tr["color"] * torch.tensor(g, dtype=torch.float64)).sum() + \
@@ -401,6 +513,27 @@ def test_oracle_scale_modifier_and_partial_degree(alt, aa, mod, rows_deg, D, rea
     assert np.all(gr["dsh"][:, active:] == 0) and np.all(tr["shs"].grad.numpy()[:, active:] == 0)
     if active:
         assert np.abs(gr["dsh"][:, :active]).max() > 0
+    return fr, gr, tr
+
+
+@pytest.mark.parametrize("kind,alt,aa,mod,rows_deg,D,realcam,W,H,bg", [
+    ("frustum", False, True, 1.7, 3, 1, None, 64, 48, (0.0, 0.0, 0.0)),
+    ("frustum", False, True, 0.5, 3, 2, 5, 60, 44, (0.3, 0.2, 0.1)),
+    ("frustum-q", True, True, 1.7, 3, 1, 5, 60, 44, (0.2, 0.4, 0.6)),
+    ("frustum", True, False, 0.5, 2, 1, None, 64, 48, (0.0, 0.0, 0.0))])
+def test_oracle_scale_modifier_and_partial_degree_on_clamp_scenes(kind, alt, aa, mod, rows_deg, D, realcam, W, H, bg):
+    """test_oracle_scale_modifier_and_partial_degree's comparison, same bounds, on the frustum-clamp scene: the modifier
+    scales the covariance the clamped Jacobian projects, and the clamped colour channels of a partial degree zero fewer
+    rows than are stored."""
+    P = 300
+    sc, cam = _clamp_scene(kind, P, rows_deg, W, H, realcam, bg)
+    sc["sh_degree"] = D
+    sc["scale_modifier"] = mod
+    if alt:
+        sc = alt_scene(sc, aa)
+    fr, gr, tr = _modifier_case(sc, cam, alt, aa, mod, rows_deg, D,
+                                1e-5 if realcam is None else _fwd_tol_far(cam, sc))
+    _assert_clamped_rows(kind, sc, cam, fr, gr, tr)
 
 
 def test_alt_oracle_culls_tiles_and_renders_bg_when_empty():
