@@ -783,6 +783,78 @@ int hlgs_hier_build(int N, int sh_floats, const float* xyz, const float* shs, co
     return check_stage(s, false, "hier_build");
 }
 
+// ---------------------------------------------------------------- hierarchy merge (hier_merge.hip)
+size_t hlgs_hier_merge_scratch_size(int n) { return merge_scratch_bytes(n); }
+
+int hlgs_hier_merge_plan(int n, int k, int K, const float* centers, const float* pos, const int* nodes, float falloff,
+                         void* scratch, int stages, void* stream)
+{
+    if (n < 1 || n > HLGS_MERGE_MAX_N) return fail(HLGS_ERR_ARG, "n must be in [1, HLGS_MERGE_MAX_N]");
+    if (K < 1 || k < 0 || k >= K) return fail(HLGS_ERR_ARG, "chunk index outside [0, K)");
+    if (!centers || !pos || !nodes || !scratch) return fail(HLGS_ERR_ARG, "missing tensor");
+    if ((uintptr_t)scratch % kAlign) return fail(HLGS_ERR_ARG, "scratch must be 256-byte aligned");
+    if (stages <= 0 || stages > HLGS_MERGE_PLAN_ALL) return fail(HLGS_ERR_ARG, "unknown stage");
+    const MergeIn in = {n, 0, pos, nullptr, nullptr, nullptr, nullptr, nodes};
+    hipStream_t s = (hipStream_t)stream;
+    hipGetLastError();
+    launch_merge_plan(in, k, K, centers, falloff, scratch, stages, s);
+    return check_stage(s, false, "hier_merge_plan");
+}
+
+static int merge_outputs(const HierOut& out)
+{
+    if (!out.pos || !out.shs || !out.alpha || !out.log_scales || !out.rot || !out.nodes)
+        return fail(HLGS_ERR_ARG, "missing output");
+    for (const void* p : {(const void*)out.pos, (const void*)out.shs, (const void*)out.log_scales,
+                          (const void*)out.rot, (const void*)out.nodes})
+        if ((uintptr_t)p % 16) return fail(HLGS_ERR_ARG, "outputs must be 16-byte aligned");
+    return HLGS_OK;
+}
+
+int hlgs_hier_merge_emit(int n, int sh_floats, int k, int K, const float* centers, const float* pos, const float* shs,
+                         const float* alpha, const float* log_scales, const float* rot, const int* nodes,
+                         const int* level_counts, int kept, int out_offset, int leaf_offset, int G, float* out_pos,
+                         float* out_shs, float* out_alpha, float* out_log_scales, float* out_rot, int* out_nodes,
+                         void* scratch, int stages, void* stream)
+{
+    if (n < 1 || n > HLGS_MERGE_MAX_N) return fail(HLGS_ERR_ARG, "n must be in [1, HLGS_MERGE_MAX_N]");
+    if (sh_floats < 1) return fail(HLGS_ERR_ARG, "sh_floats < 1");
+    if (K < 1 || k < 0 || k >= K) return fail(HLGS_ERR_ARG, "chunk index outside [0, K)");
+    if (!centers || !pos || !shs || !alpha || !log_scales || !rot || !nodes || !level_counts || !scratch)
+        return fail(HLGS_ERR_ARG, "missing tensor");
+    if ((uintptr_t)scratch % kAlign) return fail(HLGS_ERR_ARG, "scratch must be 256-byte aligned");
+    if (stages <= 0 || stages > HLGS_MERGE_EMIT_ALL) return fail(HLGS_ERR_ARG, "unknown stage");
+    const HierOut out = {out_pos, out_shs, out_alpha, out_log_scales, out_rot, out_nodes};
+    if (int rc = merge_outputs(out)) return rc;
+    if (kept < 1 || kept > n || out_offset < 1 || leaf_offset < 0 || (int64_t)out_offset + kept > G)
+        return fail(HLGS_ERR_ARG, "the chunk's kept rows do not fit rows out_offset .. of G");
+    int64_t rows = 0;
+    for (int d = 0; d <= HLGS_MERGE_MAX_DEPTH; d++) {
+        if (level_counts[d] < 0) return fail(HLGS_ERR_ARG, "negative level count");
+        rows += level_counts[d];
+    }
+    if (rows != n) return fail(HLGS_ERR_ARG, "level_counts must sum to n");
+    const MergeIn in = {n, sh_floats, pos, shs, alpha, log_scales, rot, nodes};
+    hipStream_t s = (hipStream_t)stream;
+    hipGetLastError();
+    launch_merge_emit(in, out, k, centers, level_counts, kept, out_offset, leaf_offset, k == K - 1, scratch, stages, s);
+    return check_stage(s, false, "hier_merge_emit");
+}
+
+int hlgs_hier_merge_root(int K, int sh_floats, int G, const int* chunk_roots, const float* centers, float root_scale,
+                         float* out_pos, float* out_shs, float* out_alpha, float* out_log_scales, float* out_rot,
+                         int* out_nodes, void* stream)
+{
+    if (K < 1 || sh_floats < 1 || G <= K) return fail(HLGS_ERR_ARG, "K >= 1, sh_floats >= 1 and G > K are needed");
+    if (!chunk_roots || !centers) return fail(HLGS_ERR_ARG, "missing tensor");
+    const HierOut out = {out_pos, out_shs, out_alpha, out_log_scales, out_rot, out_nodes};
+    if (int rc = merge_outputs(out)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    hipGetLastError();
+    launch_merge_root(K, sh_floats, G, chunk_roots, centers, (float)log((double)root_scale), out, s);
+    return check_stage(s, false, "hier_merge_root");
+}
+
 // ---------------------------------------------------------------- SPT streaming (stream.hip)
 size_t hlgs_upper_cut_scratch_size(int N)
 {

@@ -407,6 +407,24 @@ void launch_hier_valid(const HierIn& in, int strict, uint8_t* mask, uint32_t* st
 // stages: bit i runs HierStage i (HLGS_HIER_ALL: the build; single bits in order: the same build, stage by stage)
 void launch_hier_build(const HierIn& in, const HierOut& out, void* scratch, int stages, hipStream_t s);
 
+// hier_merge.hip: one chunk hierarchy weighted, filtered, spliced and re-linearised under the scene root.  The tree
+// passes are one launch per depth; the depths are bucketed from the validated node table.
+constexpr int kMergeLevels = HLGS_MERGE_MAX_DEPTH + 1;
+struct MergeIn {
+    int n, shf;
+    const float *pos, *shs, *alpha, *log_scales, *rot;
+    const int* nodes;
+};
+size_t merge_scratch_bytes(int n);
+// stages: bit 0 validate, bit 1 weights and counts
+void launch_merge_plan(const MergeIn& in, int k, int K, const float* centers, float falloff, void* scratch,
+                       int stages, hipStream_t s);
+// stages: bit 0 depth buckets and bottom-up, bit 1 top-down, bit 2 rows.  level_counts: host, kMergeLevels entries
+void launch_merge_emit(const MergeIn& in, const HierOut& out, int k, const float* centers, const int* level_counts,
+                       int kept, int out_offset, int leaf_offset, int last, void* scratch, int stages, hipStream_t s);
+void launch_merge_root(int K, int shf, int G, const int* roots, const float* centers, float log_scale,
+                       const HierOut& out, hipStream_t s);
+
 // mcmc.hip: opacity-weighted sampling, the position noise and the counter-based numbers of the densification round
 constexpr int kMcmcItems = 2048;  // candidates per block of the sampler's float64 prefix sum (256 threads x 8)
 size_t mcmc_sample_scratch_bytes(int64_t n);

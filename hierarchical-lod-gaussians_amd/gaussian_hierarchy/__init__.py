@@ -3,7 +3,8 @@
 `interpolate_lod`, a HIP replacement for the
 child/parent lerp `render_post` performs in Python (gaussian_renderer/__init__.py:304-339), and
 `create_dynamic_hierarchy`, the offline GaussianHierarchyCreator (mainHierarchyCreator.cpp) on the GPU
-(hlgs_core.hierarchy.build_dynamic_hierarchy).
+(hlgs_core.hierarchy.build_dynamic_hierarchy), and `merge_dynamic_hierarchies` / `merge_hierarchy_files`, the offline
+GaussianHierarchyMerger (mainHierarchyMerger.cpp) on the GPU.
 """
 import torch
 
@@ -12,11 +13,13 @@ from ._C import (expand_to_size, expand_to_size_dynamic, expand_to_target, get_i
                  get_interpolation_weights_dynamic, get_morton_indices, get_spt_cut_cuda, load_dynamic_hierarchy,
                  load_hierarchy, write_dynamic_hierarchy, write_hierarchy)
 from hlgs_core.hierarchy import build_dynamic_hierarchy as create_dynamic_hierarchy  # noqa: F401
+from hlgs_core.hierarchy import merge_dynamic_hierarchies, merge_hierarchy_files  # noqa: F401
 from hlgs_core.hierarchy import valid_gaussian_mask  # noqa: F401
 
 __all__ = ["_C", "create_dynamic_hierarchy", "expand_to_size", "expand_to_size_dynamic", "expand_to_target",
            "get_interpolation_weights", "get_interpolation_weights_dynamic", "get_morton_indices", "get_spt_cut_cuda",
-           "interpolate_lod", "load_dynamic_hierarchy", "load_hierarchy", "valid_gaussian_mask",
+           "interpolate_lod", "load_dynamic_hierarchy", "load_hierarchy", "merge_dynamic_hierarchies",
+           "merge_hierarchy_files", "valid_gaussian_mask",
            "write_dynamic_hierarchy", "write_hierarchy"]
 
 

@@ -102,6 +102,10 @@ _SIGS = {
     "hlgs_hier_scratch_size": (_sz, [_i]),
     "hlgs_hier_valid_mask": (_i, [_i, _i] + [_vp] * 7),
     "hlgs_hier_build": (_i, [_i, _i] + [_vp] * 12 + [_i, _vp]),
+    "hlgs_hier_merge_scratch_size": (_sz, [_i]),
+    "hlgs_hier_merge_plan": (_i, [_i, _i, _i, _vp, _vp, _vp, _f, _vp, _i, _vp]),
+    "hlgs_hier_merge_emit": (_i, [_i, _i, _i, _i] + [_vp] * 8 + [_i, _i, _i, _i] + [_vp] * 7 + [_i, _vp]),
+    "hlgs_hier_merge_root": (_i, [_i, _i, _i, _vp, _vp, _f] + [_vp] * 7),
     "hlgs_upper_cut_scratch_size": (_sz, [_i]),
     "hlgs_upper_tree_cut": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _i, _vp, _vp, C.POINTER(_i), _vp]),
     "hlgs_upper_tree_cut_device": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _i, _vp, _vp, _vp, _vp]),

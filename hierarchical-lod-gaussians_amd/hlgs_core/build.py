@@ -10,7 +10,7 @@ CSRC = os.path.join(PKG, "csrc")
 LIBDIR = os.path.join(PKG, "lib")
 OBJDIR = os.path.join(PKG, "build", "obj")
 LIB = os.path.join(LIBDIR, "libhlgs.so")
-SOURCES = ["scan.hip", "preprocess.hip", "raster_fwd.hip", "raster_bwd.hip", "gauss_bwd.hip", "lod.hip", "optim.hip", "act.hip", "loss.hip", "stream.hip", "knn.hip", "mcmc.hip", "hier_build.hip", "capi.hip", "hier_io.cpp", "spt_build.cpp"]
+SOURCES = ["scan.hip", "preprocess.hip", "raster_fwd.hip", "raster_bwd.hip", "gauss_bwd.hip", "lod.hip", "optim.hip", "act.hip", "loss.hip", "stream.hip", "knn.hip", "mcmc.hip", "hier_build.hip", "hier_merge.hip", "capi.hip", "hier_io.cpp", "spt_build.cpp"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("HLGS_ARCH", "gfx950")
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-munsafe-fp-atomics", "-fno-slp-vectorize", "-Wall",
@@ -33,8 +33,11 @@ def _deps_mtime():
 # what makes its box pruning exact and its output equal to the all-pairs restatement bit for bit.
 # hier_build.hip: the creator's bounds, merge weights and moments round as the reference writes them (one operation
 # at a time), which is what makes the tree, the leaf assignment and the first merged level equal to the restatement.
+# hier_merge.hip: the merger's chunk weight (distances, the linear falloff) rounds as the reference's float code does,
+# so that the kept set and every scaled opacity equal the recursive restatement bit for bit.
 PER_FILE = {"preprocess.hip": ["-ffp-contract=off"], "raster_fwd.hip": ["-ffp-contract=off"], "lod.hip": ["-ffp-contract=off"],
-            "gauss_bwd.hip": ["-ffp-contract=off"], "knn.hip": ["-ffp-contract=off"], "hier_build.hip": ["-ffp-contract=off"]}
+            "gauss_bwd.hip": ["-ffp-contract=off"], "knn.hip": ["-ffp-contract=off"], "hier_build.hip": ["-ffp-contract=off"],
+            "hier_merge.hip": ["-ffp-contract=off"]}
 
 
 def _compile(src, extra):

@@ -366,6 +366,82 @@ int hlgs_hier_build(int N, int sh_floats, const float* xyz, const float* shs, co
                     const float* scales, const float* rotations, float* pos, float* out_shs, float* alpha,
                     float* log_scales, float* rot, int* nodes, void* scratch, int stages, void* stream);
 
+/* ---- Trained chunk hierarchies merged into one scene hierarchy (the offline GaussianHierarchyMerger, on the device) ----
+ * K chunk hierarchies in the dynamic layout, as train_post.py saves them (save_hier, scene/gaussian_model.py:1115-1124),
+ * and their K chunk centres (center.txt) become one dynamic hierarchy: submodules/gaussianhierarchy
+ * hierarchy_explicit_loader.cpp:22-150, mainHierarchyMerger.cpp:94-140 and writer.cpp:99-171, carried over to rows of
+ * one Gaussian per node.  Chunk k is n rows of device float32 pos n x 3, shs n x sh_floats, alpha n (activated),
+ * log_scales n x 3, rot n x 4 and nodes n x 6 int32 {depth, parent, child_count, first_child, next_sibling,
+ * max_side_length}, without skybox rows.  Row 0 is the chunk's root; the other rows are in any order, linked by parent,
+ * child_count, first_child and next_sibling (the MCMC round appends and rewires rows, scene/gaussian_model.py
+ * :1743-1765); any child count is allowed (the output of a merge is a legal input); first_child of a row with
+ * child_count 0 is not read.  centers: K x 3 device float32.
+ *
+ *   weight (getWeight, hierarchy_explicit_loader.cpp:22-53), float32, every operation rounded on its own: the
+ *       position of row 0 is centers[k] (:147); d_j = sqrtf((dx dx + dy dy) + dz dz) to centre j; m = the smallest d_j,
+ *       j != k, starting from 1e12f (`if (d < m)`); w = 1 if d_k <= (1.0f - f) m, else 0 if d_k > (1.0f + f) m, else
+ *       a d_k + b with a = -1.0f / ((2.0f f) m), b = (1.0f + f) / (2.0f f); f = falloff (0.05 in the reference).
+ *       A NaN position gives a NaN weight.
+ *   keep  a node iff w > 0 (:106-110).  Its opacity becomes alpha w (one multiply); every other float of the row is
+ *       copied bit for bit, the log-scales included: the reference's exp on load and log on write (:84,
+ *       writer.cpp:119) is not reproduced.
+ *   splice (:112-131)  the children of a dropped node take its place, in order, in the child list of its nearest kept
+ *       ancestor.  A kept interior node whose descendants are all dropped stays, with child_count 0.
+ *   rows (populateDynamicRec, writer.cpp:99-171)  pre-order, row id == node id, the chunk under the scene root:
+ *       depth = 1 + the number of kept proper ancestors; parent = the nearest kept ancestor's id, 0 for the chunk
+ *       root; child_count = the spliced children; first_child = id + 1 for every node; next_sibling = the id of the
+ *       next child of the same parent, 0 for the last; max_side_length = for a kept node with child_count 0 in its
+ *       input, its rank among all such nodes of the output (chunk order, then pre-order: the index into the merged
+ *       `gaussians` vector, writer.cpp:123), -1 for every other node.
+ *   join (mainHierarchyMerger.cpp:107-136)  row 0 is a new root: depth 0, parent -1, child_count K, first_child 1,
+ *       next_sibling 0, max_side_length -1; the chunk roots follow in chunk order, chained by next_sibling.  With a_k
+ *       the chunk roots' output opacities: position = sum a_k c_k / max(sum a_k, 1e-12) and SH = the mean of the chunk
+ *       roots' SH rows, both summed in chunk order in float64 and rounded once; alpha = max a_k; log-scales =
+ *       (float)log((double)root_scale), so that no cut selects it (bounds[3] = 1e9 in the reference); rotation
+ *       (1, 0, 0, 0).
+ *
+ * hlgs_hier_merge_plan (per chunk) validates the links and computes the weights.  scratch: hlgs_hier_merge_scratch_size(n)
+ *   bytes of device memory, 256-byte aligned, one per chunk, kept until the chunk's emit has run.  Its first
+ *   HLGS_MERGE_HEADER_INTS + HLGS_MERGE_MAX_DEPTH + 1 int32 words are the plan's result, valid once the stream has
+ *   passed the call, and the merge's one read-back per chunk: {status, kept nodes, kept input-leaves, 5 x reserved},
+ *   then the number of rows at every depth.  status: HLGS_MERGE_STATUS_LINKS the node table is malformed;
+ *   HLGS_MERGE_STATUS_ROOT the chunk's root is dropped (a non-finite centre).  The caller treats a non-zero status as
+ *   an error.  Validation, by the first kernel and before anything follows a link: depth in [0, HLGS_MERGE_MAX_DEPTH],
+ *   child_count in [0, n); for every row but row 0, parent in [0, n), not itself, and depth = the parent's + 1; every
+ *   child list walked for child_count members, each in [1, n) and naming that parent; every row but row 0 a member of
+ *   exactly one list, row 0 of none.  (Together: the rows form one tree under row 0.)
+ * hlgs_hier_merge_emit (per chunk, after the read-back) writes the chunk's kept rows at out_offset .. out_offset + kept
+ *   of the outputs (G rows each, 16-byte aligned): kept and level_counts (host, HLGS_MERGE_MAX_DEPTH + 1 entries) as
+ *   read back; out_offset = 1 + the kept nodes of the chunks before it; leaf_offset = their kept input-leaves; K the
+ *   number of chunks (next_sibling of the last chunk's root is 0).  With a non-zero status in scratch its kernels do
+ *   nothing.
+ * hlgs_hier_merge_root writes row 0 from the K chunk-root rows chunk_roots[k] (device int32) of the outputs.
+ *
+ * n in [1, HLGS_MERGE_MAX_N], sh_floats >= 1, else HLGS_ERR_ARG.  Nothing is allocated; every launch goes to `stream`;
+ * no host synchronisation.  The tree passes are one launch per depth (data crosses workgroups at launch boundaries
+ * only); a child list is walked by one thread.  Results do not change from run to run (no float atomics; integer
+ * atomics only where their order does not matter).  Every memory index stays in range for any input bits.
+ * stages: HLGS_MERGE_PLAN_ALL / HLGS_MERGE_EMIT_ALL.  For measurement the stages can be run one call each, in order
+ * (plan: bit 0 validate, 1 weights; emit: bit 0 depth buckets and bottom-up counts, 1 top-down ids, 2 rows). */
+#define HLGS_MERGE_MAX_DEPTH 2047
+#define HLGS_MERGE_MAX_N (1 << 30)
+#define HLGS_MERGE_HEADER_INTS 8
+#define HLGS_MERGE_PLAN_ALL 0x3
+#define HLGS_MERGE_EMIT_ALL 0x7
+#define HLGS_MERGE_STATUS_LINKS 1u
+#define HLGS_MERGE_STATUS_ROOT 2u
+size_t hlgs_hier_merge_scratch_size(int n);
+int hlgs_hier_merge_plan(int n, int k, int K, const float* centers, const float* pos, const int* nodes, float falloff,
+                         void* scratch, int stages, void* stream);
+int hlgs_hier_merge_emit(int n, int sh_floats, int k, int K, const float* centers, const float* pos, const float* shs,
+                         const float* alpha, const float* log_scales, const float* rot, const int* nodes,
+                         const int* level_counts, int kept, int out_offset, int leaf_offset, int G, float* out_pos,
+                         float* out_shs, float* out_alpha, float* out_log_scales, float* out_rot, int* out_nodes,
+                         void* scratch, int stages, void* stream);
+int hlgs_hier_merge_root(int K, int sh_floats, int G, const int* chunk_roots, const float* centers, float root_scale,
+                         float* out_pos, float* out_shs, float* out_alpha, float* out_log_scales, float* out_rot,
+                         int* out_nodes, void* stream);
+
 /* ---- SPT streaming around the SPT cut (train_post.py:323-491) ---- */
 /* Coarse cut of the upper tree (GaussianModel.cut_hierarchy_on_condition with root 0, no upper-tree output,
  * leave_out_of_cut_condition = frustum_cull_spheres: scene/gaussian_model.py:364-404, 67-100, as train_post.py

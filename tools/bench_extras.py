@@ -19,6 +19,12 @@
             250k, 1M and 4M synthetic leaves with 48 SH floats: the whole build and every stage on its own (event
             times; the stages are then one call each); beside them the wall time of the recursive numpy restatement
             (tests/hier_build_ref.py) at 20,000 leaves and of synthetic.make_dynamic_hierarchy at 1M.
+  hier_merge  hlgs_core.hierarchy.merge_dynamic_hierarchies (the offline GaussianHierarchyMerger on the GPU) over K = 4
+            chunks of 250k, 1M and 4M rows each (48 SH floats; leaves uniform in a cube of half-side 3.2 around
+            centres 4 apart, the trees built by build_dynamic_hierarchy): the whole call, read-backs and allocation
+            included (median of 5, host clock), every stage by events, and the bytes the scatter must move (kept rows
+            x row bytes, read + write) over its time as a fraction of HBM; beside them the wall time of the recursive
+            numpy restatement (tests/hier_merge_ref.py) at 20,011 leaves per chunk.
   stream    train_post.py's SPT cache over the same hierarchy: SPT construction (host code), then a camera path
             of views through SPTCache.step (coarse cut, cache bookkeeping, SPT cut, write-back and load of the
             six parameters and twelve Adam moments to and from pinned host storage) and the dense Adam step of
@@ -349,6 +355,68 @@ def bench_hier_build(sizes=(250_000, 1_000_000, 4_000_000), restatement_P=20_000
     return out
 
 
+def bench_hier_merge(sizes=(250_000, 1_000_000, 4_000_000), K=4, shf=48, restatement_L=20_011):
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import hier_merge_ref as MR
+    from hlgs_core import hierarchy as H
+    cen = MR.centers_for(K)
+    row_bytes = 4 * (3 + shf + 1 + 3 + 4 + 6)
+
+    def chunks_of(L):
+        g = torch.Generator(device=DEV).manual_seed(L)
+        u = lambda *sh: torch.rand(*sh, generator=g, device=DEV)  # noqa: E731
+        out = []
+        for k in range(K):
+            xyz = torch.tensor(cen[k], device=DEV) + (u(L, 3) * 2 - 1) * 3.2
+            out.append(H.build_dynamic_hierarchy(xyz, u(L, shf) - 0.5, u(L) * 0.95 + 0.05, u(L, 3) * 0.05 + 0.005,
+                                                 u(L, 4) - 0.5))
+        return out
+
+    def wall(fn, iters=5, warmup=1):
+        ts = []
+        for i in range(warmup + iters):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            ts.append((time.perf_counter() - t0) * 1e3)
+        return float(np.median(ts[warmup:]))
+
+    out = dict(K=K, sh_floats=shf, row_bytes=row_bytes)
+    for rows in sizes:
+        print(f"hier_merge: {K} x {rows} rows", file=sys.stderr, flush=True)
+        chunks = chunks_of((rows + 1) // 2)
+        n_in = sum(int(c[0].shape[0]) for c in chunks)
+        whole = wall(lambda: H.merge_dynamic_hierarchies(chunks, cen))
+        stages = []
+        for _ in range(3):
+            ms = {}
+            res = H.merge_dynamic_hierarchies(chunks, cen, stage_ms=ms)
+            stages.append(ms)
+        G = int(res[0].shape[0])
+        depth = max(int(c[5][:, 0].max()) for c in chunks) + 1
+        st = {k: round(float(np.median([m[k] for m in stages])), 3) for k in H.MERGE_STAGES}
+        moved = 2.0 * (G - 1) * row_bytes
+        out[str(rows)] = dict(workload=f"{K} chunks x {n_in // K} rows in, {G} rows out, {depth} levels per chunk",
+                              kept_fraction=round((G - 1) / n_in, 4), merge_ms=round(whole, 3), rows_in_per_s=round(n_in / (whole * 1e-3)), stage_ms=st,
+                              scatter_GBs=round(moved / (st["scatter"] * 1e-3) / 1e9, 1),
+                              scatter_hbm_frac=round(moved / (st["scatter"] * 1e-3) / 1e9 / HBM, 3))
+        del chunks, res
+    chunks = chunks_of(restatement_L)
+    host = [tuple(t.cpu().numpy() for t in c) for c in chunks]
+    t0 = time.perf_counter()
+    ref = MR.merge_ref(host, cen)
+    ref_s = time.perf_counter() - t0
+    got = H.merge_dynamic_hierarchies(chunks, cen)
+    same = bool((got[5].cpu().numpy() == ref["nodes"]).all()) and all(
+        bool((g.cpu().numpy().reshape(-1).view(np.int32) == ref[k].reshape(-1).view(np.int32)).all())
+        for g, k in zip(got[:5], ("pos", "shs", "alpha", "log_scales", "rot")))
+    out["restatement"] = dict(workload=f"recursive numpy restatement, {K} chunks x {restatement_L} leaves, one run",
+                              s=round(ref_s, 2), gpu_ms=round(wall(lambda: H.merge_dynamic_hierarchies(chunks, cen)), 3),
+                              bitwise_equal=same)
+    return out
+
+
 def bench_stream(P, views=12):
     from hlgs_core import spt
     from hlgs_core.spt_cache import NAMES, SPTCache
@@ -427,6 +495,8 @@ def main():
         out["knn"] = bench_knn(tuple(int(v) for v in args.knn_sizes.split(",")))
     if "hier_build" in only:
         out["hier_build"] = bench_hier_build()
+    if "hier_merge" in only:
+        out["hier_merge"] = bench_hier_merge()
     if "stream" in only:
         out["stream"] = bench_stream(args.P)
     print(json.dumps(out))
