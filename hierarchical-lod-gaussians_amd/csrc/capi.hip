@@ -673,6 +673,110 @@ int hlgs_mcmc_noise(int64_t P, int64_t first_row, float* means3D, const float* o
     return check_stage(s, false, "mcmc_noise");
 }
 
+// ---------------------------------------------------------------- adaptive density control (density.hip)
+int hlgs_density_stats(int64_t P, const float* dL_dmean2D, const int* radii, float* grad_accum, float* denom,
+                       float* max_radii2D, void* stream)
+{
+    if (P < 0) return fail(HLGS_ERR_ARG, "P < 0");
+    if (P == 0) return HLGS_OK;
+    if (!dL_dmean2D || !radii || !grad_accum || !denom || !max_radii2D) return fail(HLGS_ERR_ARG, "missing tensor");
+    hipStream_t s = (hipStream_t)stream;
+    hipGetLastError();
+    launch_density_stats(P, dL_dmean2D, radii, grad_accum, denom, max_radii2D, s);
+    return check_stage(s, false, "density_stats");
+}
+
+int hlgs_density_select(int64_t P, const float* grad_accum, const float* max_radii2D, const float* opacity_raw,
+                        const uint8_t* leaf, double grad_threshold, double densify_min_opacity,
+                        double prune_min_opacity, int64_t protect_rows, uint8_t* select, uint8_t* prune, void* stream)
+{
+    if (P < 0 || protect_rows < 0) return fail(HLGS_ERR_ARG, "negative size");
+    if (P == 0) return HLGS_OK;
+    if (!grad_accum || !max_radii2D || !opacity_raw || !select || !prune) return fail(HLGS_ERR_ARG, "missing tensor");
+    hipStream_t s = (hipStream_t)stream;
+    hipGetLastError();
+    launch_density_select(P, grad_accum, max_radii2D, opacity_raw, leaf, grad_threshold, densify_min_opacity,
+                          prune_min_opacity, protect_rows, select, prune, s);
+    return check_stage(s, false, "density_select");
+}
+
+size_t hlgs_densify_scratch_size(int64_t P) { return densify_scratch_bytes(P); }
+
+int hlgs_densify_plan(int64_t P, const uint8_t* select, const uint8_t* prune, int drop_selected, void* scratch,
+                      int* counts_host, void* stream)
+{
+    if (P < 0) return fail(HLGS_ERR_ARG, "P < 0");
+    if (P > 0x7fffffff) return fail(HLGS_ERR_ARG, "rows are int32");
+    if (!counts_host) return fail(HLGS_ERR_ARG, "missing counts_host");
+    counts_host[0] = counts_host[1] = 0;
+    if (P == 0) return HLGS_OK;
+    if (!select || !scratch) return fail(HLGS_ERR_ARG, "missing tensor");
+    if ((uintptr_t)scratch % kAlign) return fail(HLGS_ERR_ARG, "scratch must be 256-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    hipGetLastError();
+    launch_densify_plan(P, select, prune, drop_selected, scratch, s);
+    if (int rc = check_stage(s, false, "densify_plan")) return rc;
+    HLGS_TRY_HIP(hipMemcpyAsync(counts_host, densify_counts(scratch, P), 2 * sizeof(int), hipMemcpyDeviceToHost, s));
+    HLGS_TRY_HIP(hipStreamSynchronize(s));
+    return HLGS_OK;
+}
+
+int hlgs_densify_emit(int T, const hlgs_densify_table* tables, int64_t P, int64_t n_kept, int64_t n_selected,
+                      int copies, int mode, const float* rotation, const float* noise, uint64_t seed, uint32_t round,
+                      void* scratch, void* stream)
+{
+    if (T < 0 || T > kMaxRowTables) return fail(HLGS_ERR_ARG, "at most 32 tables per call");
+    if (P < 0 || P > 0x7fffffff) return fail(HLGS_ERR_ARG, "P outside [0, 2^31)");
+    if (n_kept < 0 || n_kept > P || n_selected < 0 || n_selected > P) return fail(HLGS_ERR_ARG, "counts outside [0, P]");
+    if (copies < 1) return fail(HLGS_ERR_ARG, "copies < 1");
+    if (mode != HLGS_DENSIFY_CLONE && mode != HLGS_DENSIFY_SHRINK && mode != HLGS_DENSIFY_SPLIT)
+        return fail(HLGS_ERR_ARG, "unknown mode");
+    const int64_t n_out = n_kept + n_selected * copies;
+    if (n_out > 0x7fffffff - 8192) return fail(HLGS_ERR_ARG, "output rows are int32");
+    if (T == 0 || n_out == 0) return HLGS_OK;
+    if (!tables || !scratch) return fail(HLGS_ERR_ARG, "missing tensor");
+    if ((uintptr_t)scratch % kAlign) return fail(HLGS_ERR_ARG, "scratch must be 256-byte aligned");
+    hlgs_densify_table live[kMaxRowTables];
+    int n = 0;
+    bool has_xyz = false, has_scaling = false;
+    for (int t = 0; t < T; t++) {
+        const hlgs_densify_table& tb = tables[t];
+        if (tb.row_bytes < 0 || tb.row_bytes % 4 || tb.row_bytes > (1 << 24))
+            return fail(HLGS_ERR_ARG, "row_bytes must be a multiple of 4");
+        if (tb.role < HLGS_DENSIFY_COPY || tb.role > HLGS_DENSIFY_OPACITY) return fail(HLGS_ERR_ARG, "unknown role");
+        if (tb.row_bytes == 0) continue;  // f_rest at SH degree 0
+        if (!tb.src || !tb.dst) return fail(HLGS_ERR_ARG, "missing table");
+        if (((uintptr_t)tb.src | (uintptr_t)tb.dst) % 4) return fail(HLGS_ERR_ARG, "tables must be 4-byte aligned");
+        if ((tb.role == HLGS_DENSIFY_XYZ || tb.role == HLGS_DENSIFY_SCALING) && tb.row_bytes != 12)
+            return fail(HLGS_ERR_ARG, "xyz and scaling rows are 3 floats");
+        if (tb.role == HLGS_DENSIFY_OPACITY && tb.row_bytes != 4) return fail(HLGS_ERR_ARG, "opacity rows are 1 float");
+        has_xyz |= tb.role == HLGS_DENSIFY_XYZ;
+        has_scaling |= tb.role == HLGS_DENSIFY_SCALING;
+        live[n++] = tb;
+    }
+    if (mode == HLGS_DENSIFY_SPLIT && has_xyz && (!has_scaling || !rotation))
+        return fail(HLGS_ERR_ARG, "split needs the scaling table and rotation beside xyz");
+    if (n == 0) return HLGS_OK;
+    hipStream_t s = (hipStream_t)stream;
+    hipGetLastError();
+    if (launch_densify_emit(n, live, P, n_kept, n_selected, copies, mode, rotation, noise, seed, round, scratch, s))
+        return fail(HLGS_ERR_ARG, "the output tables are too large for one launch");
+    return check_stage(s, false, "densify_emit");
+}
+
+int hlgs_opacity_reset(int64_t P, int64_t protect_rows, double max_opacity, float* opacity_raw, float* exp_avg,
+                       float* exp_avg_sq, void* stream)
+{
+    if (P < 0 || protect_rows < 0) return fail(HLGS_ERR_ARG, "negative size");
+    if (!(max_opacity > 0.0 && max_opacity < 1.0)) return fail(HLGS_ERR_ARG, "max_opacity must lie in (0, 1)");
+    if (P == 0) return HLGS_OK;
+    if (!opacity_raw) return fail(HLGS_ERR_ARG, "missing tensor");
+    hipStream_t s = (hipStream_t)stream;
+    hipGetLastError();
+    launch_opacity_reset(P, protect_rows, max_opacity, opacity_raw, exp_avg, exp_avg_sq, s);
+    return check_stage(s, false, "opacity_reset");
+}
+
 int hlgs_activate_forward(int64_t n, const float* opacity_raw, const float* scaling_raw, const float* rotation_raw,
                           float* opacity, float* scales, float* rotations, void* stream)
 {

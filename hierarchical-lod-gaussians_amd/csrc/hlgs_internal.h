@@ -436,6 +436,22 @@ void launch_mcmc_noise(int64_t P, int64_t first_row, float* means, const float* 
                        hipStream_t s);
 void launch_rng_fill(int kind, uint64_t seed, uint32_t stream_id, uint64_t first, int64_t n, void* out, hipStream_t s);
 
+// density.hip: the adaptive density control of chunk training (statistics, selection, plan, emit, opacity reset)
+void launch_density_stats(int64_t P, const float* g, const int* radii, float* accum, float* denom, float* maxr,
+                          hipStream_t s);
+void launch_density_select(int64_t P, const float* accum, const float* maxr, const float* op, const uint8_t* leaf,
+                           double thr, double dmin, double pmin, int64_t protect, uint8_t* sel, uint8_t* prune,
+                           hipStream_t s);
+size_t densify_scratch_bytes(int64_t P);
+const int* densify_counts(void* scratch, int64_t P);  // device: [n_kept, n_selected] after launch_densify_plan
+void launch_densify_plan(int64_t P, const uint8_t* sel, const uint8_t* prune, int drop_selected, void* scratch,
+                         hipStream_t s);
+// tables: at most kMaxRowTables, none empty; returns non-zero when the grid would not fit
+int launch_densify_emit(int T, const hlgs_densify_table* tables, int64_t P, int64_t n_kept, int64_t n_sel, int copies,
+                        int mode, const float* rotation, const float* noise, uint64_t seed, uint32_t round,
+                        void* scratch, hipStream_t s);
+void launch_opacity_reset(int64_t P, int64_t protect, double cap, float* op, float* m, float* v, hipStream_t s);
+
 // scan.hip
 void scan_inclusive_u32(const uint32_t* in, uint32_t* out, size_t n, uint32_t* tmp, hipStream_t s);
 

@@ -70,6 +70,13 @@ class AdamTensor(C.Structure):
                 ("row_elems", C.c_int64), ("lr", C.c_double)]
 
 
+class DensifyTable(C.Structure):
+    _fields_ = [("src", _vp), ("dst", _vp), ("row_bytes", C.c_int64), ("role", _i)]
+
+
+DENSIFY_MODES = {"clone": 0, "shrink": 1, "split": 2}
+DENSIFY_COPY, DENSIFY_ZERO, DENSIFY_XYZ, DENSIFY_SCALING, DENSIFY_OPACITY = range(5)
+
 _SIGS = {
     "hlgs_last_error": (C.c_char_p, []),
     "hlgs_version": (C.c_char_p, []),
@@ -95,6 +102,14 @@ _SIGS = {
     "hlgs_mcmc_sample": (_i, [C.c_int64, _vp, C.c_int64, _vp, C.c_int64, C.c_uint64, C.c_uint32, _vp, _vp, C.c_int64,
                               _vp, _vp]),
     "hlgs_mcmc_noise": (_i, [C.c_int64, C.c_int64, _vp, _vp, _vp, _vp, _vp, C.c_double, C.c_uint64, C.c_uint32, _vp]),
+    "hlgs_density_stats": (_i, [C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "hlgs_density_select": (_i, [C.c_int64, _vp, _vp, _vp, _vp, C.c_double, C.c_double, C.c_double, C.c_int64, _vp,
+                                 _vp, _vp]),
+    "hlgs_densify_scratch_size": (_sz, [C.c_int64]),
+    "hlgs_densify_plan": (_i, [C.c_int64, _vp, _vp, _i, _vp, _vp, _vp]),
+    "hlgs_densify_emit": (_i, [_i, C.POINTER(DensifyTable), C.c_int64, C.c_int64, C.c_int64, _i, _i, _vp, _vp,
+                               C.c_uint64, C.c_uint32, _vp, _vp]),
+    "hlgs_opacity_reset": (_i, [C.c_int64, C.c_int64, C.c_double, _vp, _vp, _vp, _vp]),
     "hlgs_adam_update": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, C.c_uint32, C.c_uint32, _vp]),
     "hlgs_morton_codes": (_i, [_i, _vp, _vp, _vp, _vp, _vp]),
     "hlgs_knn_scratch_size": (_sz, [_i]),

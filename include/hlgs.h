@@ -242,6 +242,72 @@ int hlgs_mcmc_noise(int64_t P, int64_t first_row, float* means3D, const float* o
 int hlgs_adam_update(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, const uint8_t* visible,
                      float lr, float b1, float b2, float eps, uint32_t N, uint32_t M, void* stream);
 
+/* ---- adaptive density control of chunk training (train_single.py:144-155; scene/gaussian_model.py:1214-1218,
+ *      1249-1345, 1348-1531) ----
+ * The reference's own methods cannot be called (add_densification_stats is given two of its three arguments, densify*
+ * reads self.nodes, the prune is commented out), so the arithmetic of the cited lines is the contract.  All arrays are
+ * float32 device memory unless noted; P rows; rows below protect_rows (the skybox / scaffold prefix) are never
+ * selected, pruned or reset.  Nothing here allocates or keeps state. */
+/* add_densification_stats (train_single.py:147-148, gaussian_model.py:1527-1530), in place, for the rows with
+ * radii > 0: max_radii2D = max(max_radii2D, (float)radii), grad_accum = max(grad_accum, sqrt(gx^2 + gy^2)) of
+ * dL_dmean2D (P x 3; the fork's max, not upstream's sum), denom += 1.  Other rows keep their bits. */
+int hlgs_density_stats(int64_t P, const float* dL_dmean2D, const int* radii, float* grad_accum, float* denom,
+                       float* max_radii2D, void* stream);
+/* The masks of densify / densify_and_prune (:1458-1468, :1508, :1512-1514), evaluated in float64 from the float32
+ * inputs: o = sigmoid(opacity_raw), g = grad_accum with NaN as 0,
+ *   select = g max_radii2D o^(1/5) >= grad_threshold && o > densify_min_opacity && leaf && row >= protect_rows
+ *   prune  = o < prune_min_opacity && row >= protect_rows          (prune_min_opacity < 0: all zero)
+ * leaf: P bytes or NULL (every row a leaf); select, prune: P bytes each. */
+int hlgs_density_select(int64_t P, const float* grad_accum, const float* max_radii2D, const float* opacity_raw,
+                        const uint8_t* leaf, double grad_threshold, double densify_min_opacity,
+                        double prune_min_opacity, int64_t protect_rows, uint8_t* select, uint8_t* prune, void* stream);
+/* The round's plan: in ascending row order the kept rows (not pruned, and not selected when drop_selected) and the
+ * selected rows, left in scratch (hlgs_densify_scratch_size(P) bytes of device memory, 256-byte aligned) for
+ * hlgs_densify_emit.  prune may be NULL.  counts_host[0] = n_kept, counts_host[1] = n_selected, read back here: the
+ * round's only host synchronisation (the caller sizes the output tables from them); pass pinned memory. */
+size_t hlgs_densify_scratch_size(int64_t P);
+int hlgs_densify_plan(int64_t P, const uint8_t* select, const uint8_t* prune, int drop_selected, void* scratch,
+                      int* counts_host, void* stream);
+/* Every output table of the round in one launch (_prune_optimizer :1254-1258, :1279-1282; cat_tensors_to_optimizer
+ * :1302-1306).  Output row d < n_kept is input row kept[d], bit for bit; output row n_kept + copies j + k is copy k of
+ * parent selected[j] (repeat_interleave, :1473, behind torch.cat) -- the reference appends and then prunes, which is
+ * the same table because a selected row (o > 0.15) is never pruned (o < 0.005) and a new row's opacity is at least
+ * 0.15 / (0.8 copies).  A table's role says what its new rows hold:
+ *   HLGS_DENSIFY_COPY     the parent's row, bit for bit (f_dc, f_rest, rotation)
+ *   HLGS_DENSIFY_ZERO     zeros (both Adam moments of every parameter, :1302-1303; the statistics)
+ *   HLGS_DENSIFY_XYZ      (3 floats)  split: R(q / |q|) (exp(s) * xi) + xyz (:1367-1371); else a copy
+ *   HLGS_DENSIFY_SCALING  (3 floats)  shrink: log(exp(s) / (0.8 copies)) (:1474); split: log(exp(s) / (0.7 copies))
+ *                                     (:1372); clone: a copy (the reference's log(exp(s)), :1421, is not reproduced)
+ *   HLGS_DENSIFY_OPACITY  (1 float)   shrink: logit(sigmoid(x) / (0.8 copies)) (:1478); else a copy
+ * A transformed value is computed in float64 from the float32 inputs and rounded once.  xi of new row r = copies j + k,
+ * axis c: noise[3 r + c] when noise is given, else normal number 3 r + c of (seed, stream = round).  split needs the
+ * XYZ and SCALING tables and rotation (P x 4, the raw quaternions).  At most 32 tables; a table with row_bytes == 0 is
+ * skipped; row_bytes is a multiple of 4 and tables are 4-byte aligned (16-byte aligned destinations are written with
+ * 16-byte stores).  n_kept and n_selected are the plan's counts; a launch given other counts writes nothing. */
+#define HLGS_DENSIFY_CLONE 0
+#define HLGS_DENSIFY_SHRINK 1
+#define HLGS_DENSIFY_SPLIT 2
+#define HLGS_DENSIFY_COPY 0
+#define HLGS_DENSIFY_ZERO 1
+#define HLGS_DENSIFY_XYZ 2
+#define HLGS_DENSIFY_SCALING 3
+#define HLGS_DENSIFY_OPACITY 4
+typedef struct hlgs_densify_table {
+    const void* src;   /* P rows */
+    void* dst;         /* n_kept + copies n_selected rows */
+    int64_t row_bytes;
+    int role;
+} hlgs_densify_table;
+int hlgs_densify_emit(int T, const hlgs_densify_table* tables, int64_t P, int64_t n_kept, int64_t n_selected,
+                      int copies, int mode, const float* rotation, const float* noise, uint64_t seed, uint32_t round,
+                      void* scratch, void* stream);
+/* reset_opacity (:1214-1218) with replace_tensor_to_optimizer's zeroed moments (:1237-1238), in place, one pass: rows
+ * >= protect_rows with sigmoid(opacity_raw) > max_opacity (float64) take (float)logit(max_opacity), every other row
+ * keeps its bits (the reference's inverse_sigmoid(sigmoid(x)) round trip destroys very negative logits and is not
+ * reproduced); exp_avg and exp_avg_sq (either may be NULL) are zeroed for all rows. */
+int hlgs_opacity_reset(int64_t P, int64_t protect_rows, double max_opacity, float* opacity_raw, float* exp_avg,
+                       float* exp_avg_sq, void* stream);
+
 /* ---- hierarchical LOD ---- */
 size_t hlgs_lod_scratch_size(int N);
 /* nodes: N x 6 int32 HierarchyNode rows; viewpoint: device float3; viewdir: host float[3].
