@@ -809,6 +809,51 @@ int hlgs_activate_backward(int64_t n, const float* opacity, const float* scales,
     return check_stage(s, false, "activate_backward");
 }
 
+size_t hlgs_activate_reg_scratch_size(int64_t n)
+{
+    return align_up(2 * sizeof(float) * (size_t)act_reg_blocks(n > 0 ? n : 1)) + kAlign;
+}
+
+int hlgs_activate_reg_forward(int64_t n, const float* opacity_raw, const float* scaling_raw, const float* rotation_raw,
+                              float* opacity, float* scales, float* rotations, float* reg, void* scratch, void* stream)
+{
+    if (n < 0) return fail(HLGS_ERR_ARG, "negative size");
+    if (!reg || !scratch) return fail(HLGS_ERR_ARG, "missing tensor");
+    hipStream_t s = (hipStream_t)stream;
+    if (n == 0) {  // no rows: both losses are 0 (the reference would divide by zero)
+        HLGS_TRY_HIP(hipMemsetAsync(reg, 0, 2 * sizeof(float), s));
+        return HLGS_OK;
+    }
+    if (!opacity_raw || !scaling_raw || !rotation_raw || !opacity || !scales || !rotations)
+        return fail(HLGS_ERR_ARG, "missing tensor");
+    if ((reinterpret_cast<uintptr_t>(rotation_raw) | reinterpret_cast<uintptr_t>(rotations)) & 15u)
+        return fail(HLGS_ERR_ARG, "rotation rows must be 16-byte aligned");
+    if (act_reg_blocks(n) > 0x7fffffffll) return fail(HLGS_ERR_ARG, "too many rows for one launch");
+    hipGetLastError();
+    launch_act_reg_fwd(n, opacity_raw, scaling_raw, rotation_raw, opacity, scales, rotations, reg,
+                       static_cast<float*>(aligned(scratch)), s);
+    return check_stage(s, false, "activate_reg_forward");
+}
+
+int hlgs_activate_reg_backward(int64_t n, const float* opacity, const float* scales, const float* rotation_raw,
+                               const float* g_opacity, const float* g_scales, const float* g_rotations,
+                               const float* g_reg, float* d_opacity_raw, float* d_scaling_raw, float* d_rotation_raw,
+                               void* stream)
+{
+    if (n <= 0) return HLGS_OK;
+    if (((g_opacity || g_reg) && (!opacity || !d_opacity_raw)) || ((g_scales || g_reg) && (!scales || !d_scaling_raw)) ||
+        (g_rotations && (!rotation_raw || !d_rotation_raw)))
+        return fail(HLGS_ERR_ARG, "missing tensor");
+    if ((reinterpret_cast<uintptr_t>(rotation_raw) | reinterpret_cast<uintptr_t>(g_rotations) |
+         reinterpret_cast<uintptr_t>(d_rotation_raw)) & 15u)
+        return fail(HLGS_ERR_ARG, "rotation rows must be 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    hipGetLastError();
+    launch_act_reg_bwd(n, opacity, scales, rotation_raw, g_opacity, g_scales, g_rotations, g_reg, d_opacity_raw,
+                       d_scaling_raw, d_rotation_raw, s);
+    return check_stage(s, false, "activate_reg_backward");
+}
+
 int hlgs_adam_update(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, const uint8_t* visible,
                      float lr, float b1, float b2, float eps, uint32_t N, uint32_t M, void* stream)
 {

@@ -328,8 +328,18 @@ void launch_act_fwd(int64_t n, const float* op_raw, const float* sc_raw, const f
                     float* rot, hipStream_t s);
 void launch_act_bwd(int64_t n, const float* op, const float* sc, const float* rot_raw, const float* g_op,
                     const float* g_sc, const float* g_rot, float* d_op, float* d_sc, float* d_rot, hipStream_t s);
+// the same with the MCMC regularisers (train_post.py:565-576): reg = (sum op, sum sc) / n through `partial`
+// (2 floats per act_reg_blocks(n)); g_reg (device, 2 floats) = their upstream gradients, NULL: the plain backward
+int64_t act_reg_blocks(int64_t n);
+void launch_act_reg_fwd(int64_t n, const float* op_raw, const float* sc_raw, const float* rot_raw, float* op, float* sc,
+                        float* rot, float* reg, float* partial, hipStream_t s);
+void launch_act_reg_bwd(int64_t n, const float* op, const float* sc, const float* rot_raw, const float* g_op,
+                        const float* g_sc, const float* g_rot, const float* g_reg, float* d_op, float* d_sc,
+                        float* d_rot, hipStream_t s);
 
 // loss.hip
+// k_reduce_partials, one block: out[k] = s_k * sum_i partial[i * stride + k] for k < stride <= 2, in double, in index order
+void launch_reduce_partials(int n, int stride, const float* partial, double s0, double s1, float* out, hipStream_t s);
 size_t ssim_partials(int C, int H, int W);
 void launch_ssim_forward(int C, int H, int W, const float* img1, const float* img2, int valid, float* abc,
                          float* partial, float* out, hipStream_t s, bool clamp1);

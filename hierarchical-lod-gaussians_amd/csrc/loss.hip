@@ -645,6 +645,11 @@ void launch_photo_backward(int H, int W, const float* image, const float* gt, co
         hipLaunchKernelGGL(k_reduce_expo_grad, dim3(1), dim3(768), 0, s, (int)(g.x * g.y), partial, grad_expo);
 }
 
+void launch_reduce_partials(int n, int stride, const float* partial, double s0, double s1, float* out, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(1024), 0, s, n, stride, partial, s0, s1, out);
+}
+
 int depth_l1_blocks(long n) { return (int)std::min<long>(2048, (n + 255) / 256); }
 
 void launch_depth_l1_forward(long n, const float* inv, const float* mono, const float* mask, float* partial,

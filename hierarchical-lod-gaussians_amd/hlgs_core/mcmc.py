@@ -5,6 +5,7 @@ position noise (:868-878) on the HIP path.
                            probabilities of its callers (:1614, :1714): hlgs_mcmc_sample, on the GPU, reading the opacity
                            column where it lies (device memory, or the packed pinned rows of SPTCache.host)
   position_noise_(...)     train_post.py:868-878: hlgs_mcmc_noise, one pass, in place
+  add_regularizers(...)    train_post.py:573-576: the opacity and scale regularisers of activate_regularized, weighted
   update_params(...)       GaussianModel._update_params (:1569-1578) through compute_relocation
   add_new_gs(...)          GaussianModel.add_new_gs (:1700-1774); its node and row writes are apply_spawn (no GPU)
   relocate_gs(...)         GaussianModel.relocate_gs (:1588-1698); its node and row writes are apply_relocation (no GPU)
@@ -16,7 +17,8 @@ int32 HierarchyNode rows on the host.  Rows are written in place and nothing is 
 
 Random numbers are the counter-based ones of csrc/hlgs_rng.h: a round is a function of (inputs, seed).  Stream 0 of the
 seed samples the spawn, stream 1 the relocation; the host permutation of relocate_gs uses a torch.Generator seeded
-with the seed.  Differences from the reference are listed in DESIGN.md §6 (A-25 to A-32).
+with the seed.  Differences from the reference are listed in DESIGN.md §6 (A-25 to A-32; A-42 to A-44 for the
+regularisers).
 """
 import torch
 
@@ -121,6 +123,19 @@ def position_noise_(means3D, opacity_raw, scaling_raw, rotation_raw, noise_lr, x
                                 L.ptr(rotation_raw), L.ptr(noise), float(noise_lr) * float(xyz_lr),
                                 int(seed or 0), int(step), L.stream()))
     return means3D
+
+
+def add_regularizers(loss, opacity_loss, scaling_loss, lambda_opacity=0.01, lambda_scaling=0.0):
+    """train_post.py:573-576: loss + lambda_opacity * opacity_loss + lambda_scaling * scaling_loss, each term only when
+    its lambda is > 0 (the defaults are the reference's, :74-75), so that with lambda_scaling = 0 an overflowed
+    scaling_loss (inf) cannot turn the loss into NaN through 0 * inf; with both lambdas 0 `loss` itself is returned.
+    opacity_loss and scaling_loss are the last two results of hlgs_core.activations.activate_regularized; they are also
+    what train_post.py:659-660 logs: "Mean Opacity" = opacity_loss and "Mean Scaling" = scaling_loss / 3."""
+    if lambda_opacity > 0:
+        loss = loss + lambda_opacity * opacity_loss
+    if lambda_scaling > 0:
+        loss = loss + lambda_scaling * scaling_loss
+    return loss
 
 
 def _inverse_sigmoid(x):

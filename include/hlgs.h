@@ -668,6 +668,25 @@ int hlgs_activate_forward(int64_t n, const float* opacity_raw, const float* scal
 int hlgs_activate_backward(int64_t n, const float* opacity, const float* scales, const float* rotation_raw,
                            const float* g_opacity, const float* g_scales, const float* g_rotations, float* d_opacity_raw,
                            float* d_scaling_raw, float* d_rotation_raw, void* stream);
+/* The same pass with the two regularisers of the MCMC training step (train_post.py:565-576): reg (device, 2 floats) =
+ * (opacity_loss, scaling_loss) = (sum_i opacity_i / n, sum_i sum_k scales_ik / n) over the n rows passed in -- the
+ * reference's sum(|.|) / len(render_indices); the activated values are positive, and the scaling sum over 3 n values
+ * is divided by n as there.  The three activated outputs are bit-identical to hlgs_activate_forward's.  The sums are
+ * workgroup partials added in double in a fixed order (no float atomics): reg does not change from run to run.
+ * reg and scratch (hlgs_activate_reg_scratch_size(n) bytes) are required; n == 0 writes reg = (0, 0) on the stream and
+ * launches no kernel. */
+size_t hlgs_activate_reg_scratch_size(int64_t n);
+int hlgs_activate_reg_forward(int64_t n, const float* opacity_raw, const float* scaling_raw, const float* rotation_raw,
+                              float* opacity, float* scales, float* rotations, float* reg /* device, 2 floats */,
+                              void* scratch, void* stream);
+/* hlgs_activate_backward with the regularisers' upstream gradients g_reg = (dL/d opacity_loss, dL/d scaling_loss),
+ * read on the device: d_opacity_raw = ((g_opacity + g_reg[0] / n) (1 - o)) o, d_scaling_raw = (g_scales + g_reg[1] / n) s.
+ * With g_reg non-NULL a NULL g_opacity / g_scales counts as 0, and opacity, scales, d_opacity_raw and d_scaling_raw are
+ * required; with g_reg NULL this is hlgs_activate_backward. */
+int hlgs_activate_reg_backward(int64_t n, const float* opacity, const float* scales, const float* rotation_raw,
+                               const float* g_opacity, const float* g_scales, const float* g_rotations,
+                               const float* g_reg /* device, 2 floats, or NULL */,
+                               float* d_opacity_raw, float* d_scaling_raw, float* d_rotation_raw, void* stream);
 
 /* ---- photometric losses of the training step (utils/loss_utils.py:17-63, train_single.py:106-121,
  *      train_post.py:558-559 with the un-vendored fused_ssim) ---- */

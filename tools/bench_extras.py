@@ -10,6 +10,9 @@
   loss_exp  the same loss for a view with a trained (3, 4) exposure and an alpha mask (clamp_image=True), gradients to
             the image and the exposure: the fused call beside the torch composition it replaces, alternated, three
             runs each.
+  act_reg   the parameter activations of --P resident rows with the MCMC opacity and scale regularisers
+            (train_post.py:565-576), forward + backward: activate() alone, activate() plus the torch expression of the
+            two terms, and activate_regularized, alternated, three runs each.
   adam      SparseGaussianAdam.step over 1M Gaussians (59 floats each, six parameter groups), half visible.
   morton    get_morton_indices over the hierarchy's nodes.
   knn       simple_knn.distCUDA2 (create_from_pcd's initial scales) at 250k, 1M and 4M points on a uniform cube and
@@ -163,6 +166,52 @@ def bench_loss_exp(W, H, legs=("fused", "composed"), runs=3):
         alg = N * (28 + 36 + 64 + 12)
         out["fused_alg_GBs"] = round(alg / (min(ms["fused"]) * 1e-3) / 1e9, 1)
     return out
+
+
+def bench_act_reg(P, runs=3):
+    """The activations of P resident rows with the MCMC regularisers (train_post.py:565-576), forward + backward with
+    upstream gradients on the three activated outputs and loss = 0.01 opacity_loss + 0.02 scaling_loss: `activate` is
+    activate() alone (no regularisers), `composed` is activate() plus the torch expression of the two terms, which is
+    what a caller wrote before activate_regularized, and `fused` is activate_regularized.  Each run is timed()'s
+    median; the legs alternate, `runs` runs each.  fused_le_composed is the condition the fused call has to meet;
+    fused_minus_activate_ms is what the regularisers cost."""
+    from hlgs_core.activations import activate, activate_regularized
+    from hlgs_core.mcmc import add_regularizers
+    g = torch.Generator(device=DEV).manual_seed(0)
+    op = (torch.randn((P, 1), device=DEV, generator=g) * 4).requires_grad_(True)
+    sc = (torch.randn((P, 3), device=DEV, generator=g) * 2 - 4).requires_grad_(True)
+    rot = torch.randn((P, 4), device=DEV, generator=g).requires_grad_(True)
+    ups = [torch.randn(s, device=DEV, generator=g) for s in ((P, 1), (P, 3), (P, 4))]
+
+    def clear():
+        op.grad = sc.grad = rot.grad = None
+
+    def plain():
+        clear()
+        torch.autograd.backward(activate(op, sc, rot), ups)
+
+    def composed():
+        clear()
+        o, s, r = activate(op, sc, rot)
+        loss = add_regularizers(0.0, torch.sum(torch.abs(o)) / P, torch.sum(torch.abs(s)) / P, 0.01, 0.02)
+        torch.autograd.backward([o, s, r, loss], ups + [None])
+
+    def fused():
+        clear()
+        o, s, r, ol, sl = activate_regularized(op, sc, rot)
+        torch.autograd.backward([o, s, r, add_regularizers(0.0, ol, sl, 0.01, 0.02)], ups + [None])
+
+    fns = dict(activate=plain, composed=composed, fused=fused)
+    ms = {k: [] for k in fns}
+    for _ in range(runs):
+        for k, fn in fns.items():
+            ms[k].append(round(timed(fn, iters=50, warmup=5), 4))
+    med = {k: round(float(np.median(v)), 4) for k, v in ms.items()}
+    alg = P * 4 * (8 + 8 + 8 + 8 + 8)  # fwd: 8 floats read, 8 written; bwd: 8 + 8 read (rows, upstream), 8 written
+    return dict(workload=f"activations of {P} rows with the opacity and scale regularisers, fwd+bwd", runs_ms=ms,
+                median_ms=med, fused_le_composed=bool(med["fused"] <= med["composed"]),
+                fused_minus_activate_ms=round(med["fused"] - med["activate"], 4),
+                fused_alg_GBs=round(alg / (med["fused"] * 1e-3) / 1e9, 1))
 
 
 def bench_adam(P):
@@ -486,6 +535,8 @@ def main():
         out["loss"] = bench_loss(args.W, args.H)
     if "loss_exp" in only:
         out["loss_exp"] = bench_loss_exp(args.W, args.H)
+    if "act_reg" in only:
+        out["act_reg"] = bench_act_reg(args.P)
     if "adam" in only:
         out["adam"] = bench_adam(args.P)
     if "lod" in only:
