@@ -932,6 +932,50 @@ int hlgs_hier_build(int N, int sh_floats, const float* xyz, const float* shs, co
     return check_stage(s, false, "hier_build");
 }
 
+// ---------------------------------------------------------------- SPT build on the device (spt_build.hip)
+size_t hlgs_spt_device_scratch_size(int G) { return spt_device_scratch_bytes(G); }
+
+int hlgs_spt_build_device(int G, const int* nodes, const float* xyz, int64_t xyz_stride, const float* log_scales,
+                          int64_t scale_stride, int root, float spt_root_volume, float target_granularity,
+                          int min_spt_size, void* scratch, int stages, int* sizes, int* host_syncs, void* stream)
+{
+    if (host_syncs) *host_syncs = 0;
+    if (G <= 0 || G > HLGS_SPT_MAX_G || root < 0 || root >= G || !nodes || !xyz || !log_scales)
+        return fail(HLGS_ERR_ARG, "invalid hierarchy arguments");
+    if (xyz_stride < 3 || scale_stride < 3) return fail(HLGS_ERR_ARG, "row strides must be at least 3 floats");
+    if (!scratch || !sizes) return fail(HLGS_ERR_ARG, "missing scratch or sizes");
+    if ((uintptr_t)scratch % kAlign) return fail(HLGS_ERR_ARG, "scratch must be 256-byte aligned");
+    if (stages <= 0 || stages > HLGS_SPT_STAGE_ALL) return fail(HLGS_ERR_ARG, "unknown stage");
+    sizes[0] = sizes[1] = sizes[2] = 0;
+    hipStream_t s = (hipStream_t)stream;
+    hipGetLastError();
+    if (int rc = spt_device_build(G, nodes, xyz, xyz_stride, log_scales, scale_stride, root, spt_root_volume,
+                                  target_granularity, min_spt_size, scratch, stages, sizes, host_syncs, s)) {
+        hipGetLastError();
+        return rc;
+    }
+    return check_stage(s, false, "spt_build_device");
+}
+
+int hlgs_spt_emit_device(int G, const int* nodes, void* scratch, int n_spt, int n_entries, int n_upper, int* starts,
+                         float* smax, float* smin, int* gidx, int* roots, int* up_nodes, float* up_xyz,
+                         float* up_scaling, float* min_d2, float* radii, void* stream)
+{
+    if (G <= 0 || G > HLGS_SPT_MAX_G || !nodes || !scratch) return fail(HLGS_ERR_ARG, "invalid hierarchy arguments");
+    if ((uintptr_t)scratch % kAlign) return fail(HLGS_ERR_ARG, "scratch must be 256-byte aligned");
+    if (n_spt < 0 || n_entries < 0 || n_upper < 1 || n_spt > G || n_entries > G || n_upper > G)
+        return fail(HLGS_ERR_ARG, "sizes are not those of a build over G nodes");
+    if (!starts || !up_nodes || !up_xyz || !up_scaling || !min_d2 || (n_spt && !roots) ||
+        (n_entries && (!smax || !smin || !gidx)))
+        return fail(HLGS_ERR_ARG, "missing output");
+    hipStream_t s = (hipStream_t)stream;
+    hipGetLastError();
+    if (int rc = spt_device_emit(G, nodes, scratch, n_spt, n_entries, n_upper, starts, smax, smin, gidx, roots,
+                                 up_nodes, up_xyz, up_scaling, min_d2, radii, s))
+        return rc;
+    return check_stage(s, false, "spt_emit_device");
+}
+
 // ---------------------------------------------------------------- hierarchy merge (hier_merge.hip)
 size_t hlgs_hier_merge_scratch_size(int n) { return merge_scratch_bytes(n); }
 

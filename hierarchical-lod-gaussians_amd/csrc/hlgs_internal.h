@@ -462,6 +462,16 @@ int launch_densify_emit(int T, const hlgs_densify_table* tables, int64_t P, int6
                         void* scratch, hipStream_t s);
 void launch_opacity_reset(int64_t P, int64_t protect, double cap, float* op, float* m, float* v, hipStream_t s);
 
+// spt_build.hip: the SPTs and the upper tree of a dynamic hierarchy (the device restatement of spt_build.cpp).
+// Both return an HLGS_* code (the message set); sizes = {n_spt, n_entries, n_upper}
+size_t spt_device_scratch_bytes(int G);
+int spt_device_build(int G, const int* nodes, const float* xyz, int64_t xyz_stride, const float* log_scales,
+                     int64_t scale_stride, int root, float volume, float tg, int min_size, void* scratch, int stages,
+                     int* sizes, int* syncs, hipStream_t s);
+int spt_device_emit(int G, const int* nodes, void* scratch, int n_spt, int n_entries, int n_upper, int* starts,
+                     float* smax, float* smin, int* gidx, int* roots, int* up_nodes, float* up_xyz, float* up_scaling,
+                     float* min_d2, float* radii, hipStream_t s);
+
 // scan.hip
 void scan_inclusive_u32(const uint32_t* in, uint32_t* out, size_t n, uint32_t* tmp, hipStream_t s);
 

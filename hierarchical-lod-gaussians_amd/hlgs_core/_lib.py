@@ -146,6 +146,10 @@ _SIGS = {
     "hlgs_spt_result_sizes": (_i, [_vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
     "hlgs_spt_result_copy": (_i, [_vp] * 11),
     "hlgs_spt_result_free": (None, [_vp]),
+    "hlgs_spt_device_scratch_size": (_sz, [_i]),
+    "hlgs_spt_build_device": (_i, [_i, _vp, _vp, C.c_int64, _vp, C.c_int64, _i, _f, _f, _i, _vp, _i, C.POINTER(_i),
+                                   C.POINTER(_i), _vp]),
+    "hlgs_spt_emit_device": (_i, [_i, _vp, _vp, _i, _i, _i] + [_vp] * 11),
     "hlgs_scatter_rows": (_i, [C.c_int64, _i, _vp, _vp, _vp, _vp]),
     "hlgs_ssim_scratch_size": (_sz, [_i, _i, _i]),
     "hlgs_ssim_forward": (_i, [_i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),

@@ -10,7 +10,7 @@ CSRC = os.path.join(PKG, "csrc")
 LIBDIR = os.path.join(PKG, "lib")
 OBJDIR = os.path.join(PKG, "build", "obj")
 LIB = os.path.join(LIBDIR, "libhlgs.so")
-SOURCES = ["scan.hip", "preprocess.hip", "raster_fwd.hip", "raster_bwd.hip", "gauss_bwd.hip", "lod.hip", "optim.hip", "act.hip", "loss.hip", "stream.hip", "knn.hip", "mcmc.hip", "density.hip", "hier_build.hip", "hier_merge.hip", "capi.hip", "hier_io.cpp", "spt_build.cpp"]
+SOURCES = ["scan.hip", "preprocess.hip", "raster_fwd.hip", "raster_bwd.hip", "gauss_bwd.hip", "lod.hip", "optim.hip", "act.hip", "loss.hip", "stream.hip", "knn.hip", "mcmc.hip", "density.hip", "hier_build.hip", "hier_merge.hip", "spt_build.hip", "capi.hip", "hier_io.cpp", "spt_build.cpp"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("HLGS_ARCH", "gfx950")
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-munsafe-fp-atomics", "-fno-slp-vectorize", "-Wall",
@@ -35,15 +35,25 @@ def _deps_mtime():
 # at a time), which is what makes the tree, the leaf assignment and the first merged level equal to the restatement.
 # hier_merge.hip: the merger's chunk weight (distances, the linear falloff) rounds as the reference's float code does,
 # so that the kept set and every scaled opacity equal the recursive restatement bit for bit.
+# spt_build.hip: the SPT build's volumes, s0*s1 + s0*s2 + s1*s2 and squared distances round as the host build's
+# (spt_build.cpp, one operation at a time), so that the cut, the kept SPTs and the sort equal it bit for bit.
 # density.hip is not in the list: its transforms and its selection rule run in float64 and are compared with a float64
 # restatement to a rounding or two, its copies are bit copies, and no result of it has to equal a float32 restatement.
 PER_FILE = {"preprocess.hip": ["-ffp-contract=off"], "raster_fwd.hip": ["-ffp-contract=off"], "lod.hip": ["-ffp-contract=off"],
             "gauss_bwd.hip": ["-ffp-contract=off"], "knn.hip": ["-ffp-contract=off"], "hier_build.hip": ["-ffp-contract=off"],
-            "hier_merge.hip": ["-ffp-contract=off"]}
+            "hier_merge.hip": ["-ffp-contract=off"], "spt_build.hip": ["-ffp-contract=off"]}
+
+
+def obj_name(src):
+    """Object file of a source: its stem, with the extension kept where two sources share the stem (spt_build.cpp, the
+    host build, and spt_build.hip, the device build)."""
+    stem = os.path.splitext(src)[0]
+    shared = sum(os.path.splitext(s)[0] == stem for s in SOURCES) > 1
+    return (src.replace(".", "_") if shared else stem) + ".o"
 
 
 def _compile(src, extra):
-    obj = os.path.join(OBJDIR, os.path.splitext(src)[0] + ".o")
+    obj = os.path.join(OBJDIR, obj_name(src))
     cmd = [HIPCC] + FLAGS + PER_FILE.get(src, []) + extra + ["-c", os.path.join(CSRC, src), "-o", obj]
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:

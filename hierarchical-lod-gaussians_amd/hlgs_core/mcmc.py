@@ -307,13 +307,16 @@ def relocate_gs(storage, opt_storage, nodes, dead_mask, size, skybox_points, *, 
     return int(dead.numel())
 
 
-def densify_round(cache, nodes, size, *, cap_max, seed, spt_args, min_opacity=0.005, device="cuda"):
+def densify_round(cache, nodes, size, *, cap_max, seed, spt_args, min_opacity=0.005, device="cuda",
+                  spt_on_device=False):
     """One densification round of train_post.py:710-767 around an SPTCache whose storage has spare capacity: the
     cache is emptied into storage (cache.reset), leaves are spawned (add_new_gs), the leaves that were at or below
     min_opacity before the spawn are relocated (relocate_gs), the SPTs are rebuilt and handed to the cache
     (cache.reset(spt)).  spt_args: the keyword arguments of build_hierarchical_spt after `root` (SPT_Root_Volume,
-    target_granularity, ...); root defaults to the skybox size.  Returns the new size."""
-    from hlgs_core.spt import build_hierarchical_spt
+    target_granularity, ...); root defaults to the skybox size.  spt_on_device: rebuild with
+    build_hierarchical_spt_device, which reads nodes[:new_size] and the storage views where they lie (no host copy of
+    the parameter columns) and leaves the SPT arrays on the device; otherwise the host build.  Returns the new size."""
+    from hlgs_core.spt import build_hierarchical_spt, build_hierarchical_spt_device
     size = int(size)
     cache.reset()
     storage, opt_storage = cache.storage, cache.opt_storage
@@ -327,7 +330,11 @@ def densify_round(cache, nodes, size, *, cap_max, seed, spt_args, min_opacity=0.
     relocate_gs(storage, opt_storage, nodes, dead_mask, new_size, cache.sky, seed=seed, device=device)
     args = dict(spt_args)
     root = args.pop("root", cache.sky)
-    spt = build_hierarchical_spt(nodes[:new_size], storage["xyz"][:new_size], storage["scaling"][:new_size], root,
-                                 **args)
+    if spt_on_device:
+        spt = build_hierarchical_spt_device(nodes[:new_size], storage["xyz"][:new_size], storage["scaling"][:new_size],
+                                            root, **args, device=device)
+    else:
+        spt = build_hierarchical_spt(nodes[:new_size], storage["xyz"][:new_size], storage["scaling"][:new_size], root,
+                                     **args)
     cache.reset(spt)
     return new_size

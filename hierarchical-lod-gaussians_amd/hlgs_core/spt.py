@@ -11,6 +11,8 @@ cache traffic of train_post.py's SPT cache, on the HIP path.
                                         reads and writes directly
   build_hierarchical_spt(...)           GaussianModel.build_hierarchical_SPT (gaussian_model.py:184-332) in the
                                         library's host code
+  build_hierarchical_spt_device(...)    the same on the GPU (csrc/spt_build.hip): device tensors in and out, the
+                                        parameter columns read where they lie
   spt_view_cut(...)                     the per-view cut of get_SPT_cut (gaussian_model.py:108-159): coarse cut,
                                         SPT leaves through get_spt_cut_cuda, the cut's non-leaf nodes
 """
@@ -167,4 +169,66 @@ def build_hierarchical_spt(nodes, xyz, scaling, root, SPT_Root_Volume, target_gr
         L.check(lib.hlgs_spt_result_copy(h, *[L.ptr(out[k]) if out[k] is not None else None for k in order]))
     finally:
         lib.hlgs_spt_result_free(h)
+    return out
+
+
+SPT_KEYS = ("SPT_starts", "SPT_max", "SPT_min", "SPT_gaussian_indices", "SPT_root_hierarchy_indices",
+            "upper_tree_nodes", "upper_tree_xyz", "upper_tree_scaling", "min_distance_squared",
+            "bounding_sphere_radii")
+last_device_build = {}  # host_syncs and sizes of the last build_hierarchical_spt_device call (measurement)
+
+
+def _rows3(t, device):
+    """A (G, 3) float32 table as (tensor to keep alive, row stride in floats): device memory and pinned host memory are
+    read in place, whatever their row stride; pageable host memory is copied to the device first."""
+    t = t.detach()
+    if t.dim() != 2 or t.shape[1] != 3:
+        raise RuntimeError("xyz and scaling must be (G, 3) tensors")
+    in_place = t.dtype == torch.float32 and (t.is_cuda or t.is_pinned()) and \
+        (t.shape[0] <= 1 or (t.stride(1) == 1 and t.stride(0) >= 3))
+    if not in_place:
+        t = t.to(device=device, dtype=torch.float32).contiguous()
+    return t, (int(t.stride(0)) if t.shape[0] > 1 else 3)
+
+
+def build_hierarchical_spt_device(nodes, xyz, scaling, root, SPT_Root_Volume, target_granularity, min_SPT_Size=100,
+                                  use_bounding_spheres=True, device="cuda", stages=None):
+    """build_hierarchical_spt on the GPU (GaussianModel.build_hierarchical_SPT, gaussian_model.py:184-345): the same
+    dict, as device tensors (bounding_sphere_radii None without bounding spheres), which SPTCache._set_spt takes as
+    it is.  nodes: (G, 6) integer HierarchyNode rows on the device or the host; xyz, scaling: (G, 3) float32 on the
+    device or in pinned host memory with any row stride -- the views of SPTCache.storage are read in place -- or in
+    pageable host memory, which is copied first.  Raises RuntimeError for a hierarchy the walks cannot follow (a link
+    out of range, a node reached twice, a first child without a sibling).  stages: measurement only (a bit mask of
+    hlgs.h's HLGS_SPT_STAGE_*; without the walk stage nothing is returned)."""
+    lib = L.load()
+    L.require_gpu()
+    dev = torch.device(device)
+    nd = nodes.detach().to(device=dev, dtype=torch.int32).contiguous()
+    if nd.dim() != 2 or nd.shape[1] != 6:
+        raise RuntimeError("nodes must be (G, 6) HierarchyNode rows")
+    G = int(nd.shape[0])
+    p, sp = _rows3(xyz, dev)
+    sc, ss = _rows3(scaling, dev)
+    if p.shape[0] != G or sc.shape[0] != G:
+        raise RuntimeError("nodes, xyz and scaling must have one row per node")
+    scratch = torch.empty((lib.hlgs_spt_device_scratch_size(G) + 256,), dtype=torch.uint8, device=dev)
+    scratch = scratch[-scratch.data_ptr() % 256:]
+    sizes, syncs = (C.c_int * 3)(), C.c_int(0)
+    st = 3 if stages is None else int(stages)
+    rc = lib.hlgs_spt_build_device(G, L.ptr(nd), L.ptr(p), sp, L.ptr(sc), ss, int(root), float(SPT_Root_Volume),
+                                   float(target_granularity), int(min_SPT_Size), L.ptr(scratch), st, sizes,
+                                   C.byref(syncs), L.stream())
+    ns, ne, nu = (int(v) for v in sizes)
+    last_device_build.update(host_syncs=syncs.value, n_spt=ns, n_entries=ne, n_upper=nu)
+    L.check(rc)
+    if not st & 2:
+        return None
+    i32 = lambda *s: torch.empty(s, dtype=torch.int32, device=dev)  # noqa: E731
+    f32 = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)  # noqa: E731
+    out = dict(SPT_starts=i32(ns + 1), SPT_max=f32(ne), SPT_min=f32(ne), SPT_gaussian_indices=i32(ne),
+               SPT_root_hierarchy_indices=i32(ns), upper_tree_nodes=i32(nu, 6), upper_tree_xyz=f32(nu, 3),
+               upper_tree_scaling=f32(nu, 3), min_distance_squared=f32(nu),
+               bounding_sphere_radii=f32(nu) if use_bounding_spheres else None)
+    L.check(lib.hlgs_spt_emit_device(G, L.ptr(nd), L.ptr(scratch), ns, ne, nu,
+                                     *[L.ptr(out[k]) if out[k] is not None else None for k in SPT_KEYS], L.stream()))
     return out

@@ -568,6 +568,35 @@ int hlgs_spt_result_sizes(const hlgs_spt_result* r, int* n_spt, int* n_entries, 
 int hlgs_spt_result_copy(const hlgs_spt_result* r, int* starts, float* smax, float* smin, int* gidx, int* roots,
                          int* up_nodes, float* up_xyz, float* up_scaling, float* min_d2, float* radii);
 void hlgs_spt_result_free(hlgs_spt_result* r);
+/* The same construction (GaussianModel.build_hierarchical_SPT + get_min_distance, scene/gaussian_model.py:184-345) on
+ * the GPU, in two phases around the sizes, which are known only once the walks have ended.
+ * hlgs_spt_device_scratch_size(G): bytes of device scratch (256-byte aligned) both calls take, a function of G alone.
+ * hlgs_spt_build_device (scene/gaussian_model.py:184-345): nodes G x 6 int32 in device memory; xyz and log_scales rows
+ *   of 3 floats every xyz_stride / scale_stride floats (>= 3), in device memory or pinned host memory (the strided
+ *   views of a packed host table are read in place and packed into scratch in one pass).  Links are validated before
+ *   any is followed (first_child >= G anywhere; next_sibling >= G on a row that is some node's first child); a link
+ *   out of range, a node reached twice (a cycle or a shared child) and a first child without a second one return
+ *   HLGS_ERR_ARG.  Everything stays in scratch; sizes = {n_spt, n_entries, n_upper}.  host_syncs (may be NULL)
+ *   receives the number of read-backs the call made: one after the validation, one per level of the two walks, one
+ *   for the number of candidate SPTs and one for the sizes and the error word.
+ *   stages: HLGS_SPT_STAGE_ALL; for measurement HLGS_SPT_STAGE_PACK (staging and validation kernels only), then
+ *   HLGS_SPT_STAGE_WALK (the rest) on the same scratch.
+ * hlgs_spt_emit_device (scene/gaussian_model.py:184-345): writes the ten arrays of hlgs_spt_result_copy, in that
+ *   order, into caller-allocated device memory sized from the build's sizes (starts n_spt + 1); radii may be NULL
+ *   (no bounding spheres).  nodes and scratch as given to the build, unchanged in between.
+ * Integer outputs, up_xyz and up_scaling equal the host build's; the distances differ from it only where the
+ * correctly rounded float32 exponential differs from libm's expf. */
+#define HLGS_SPT_STAGE_PACK 1
+#define HLGS_SPT_STAGE_WALK 2
+#define HLGS_SPT_STAGE_ALL 3
+#define HLGS_SPT_MAX_G (1 << 30)
+size_t hlgs_spt_device_scratch_size(int G);
+int hlgs_spt_build_device(int G, const int* nodes, const float* xyz, int64_t xyz_stride, const float* log_scales,
+                          int64_t scale_stride, int root, float spt_root_volume, float target_granularity,
+                          int min_spt_size, void* scratch, int stages, int* sizes, int* host_syncs, void* stream);
+int hlgs_spt_emit_device(int G, const int* nodes, void* scratch, int n_spt, int n_entries, int n_upper, int* starts,
+                         float* smax, float* smin, int* gidx, int* roots, int* up_nodes, float* up_xyz,
+                         float* up_scaling, float* min_d2, float* radii, void* stream);
 /* Row gather dst[i] = src[idx[i]] and scatter dst[idx[i]] = src[i] for n rows of row_bytes (a multiple of 4):
  * the streaming cache's storage[idx].cuda() loads and write-backs (train_post.py:439-488).  src / dst may be
  * pinned host memory (read and written by the GPU over the host link). */

@@ -83,8 +83,8 @@ def with_patch(name, patch):
     odir = os.path.join(PKG, "build", "var", name, "obj")
     with cf.ThreadPoolExecutor(max_workers=8) as ex:
         new = dict(zip(rebuild, ex.map(lambda f: _compile(os.path.join(tree, CSRC_REL, f), f,
-                                                          os.path.join(odir, os.path.splitext(f)[0] + ".o")), rebuild)))
-    objs = [new.get(s, os.path.join(B.OBJDIR, os.path.splitext(s)[0] + ".o")) for s in B.SOURCES]
+                                                          os.path.join(odir, B.obj_name(f))), rebuild)))
+    objs = [new.get(s, os.path.join(B.OBJDIR, B.obj_name(s))) for s in B.SOURCES]
     return _link(name, objs)
 
 
@@ -93,8 +93,8 @@ def with_file(name, src_text, replaces):
     tree = _scratch_tree(name)
     path = os.path.join(tree, CSRC_REL, replaces)
     open(path, "w").write(src_text)
-    obj = _compile(path, replaces, os.path.join(PKG, "build", "var", name, "obj", os.path.splitext(replaces)[0] + ".o"))
-    objs = [obj if s == replaces else os.path.join(B.OBJDIR, os.path.splitext(s)[0] + ".o") for s in B.SOURCES]
+    obj = _compile(path, replaces, os.path.join(PKG, "build", "var", name, "obj", B.obj_name(replaces)))
+    objs = [obj if s == replaces else os.path.join(B.OBJDIR, B.obj_name(s)) for s in B.SOURCES]
     return _link(name, objs)
 
 
@@ -104,7 +104,7 @@ def with_defs(name, defs):
     os.makedirs(odir, exist_ok=True)
 
     def one(src):
-        obj = os.path.join(odir, os.path.splitext(src)[0] + ".o")
+        obj = os.path.join(odir, B.obj_name(src))
         subprocess.run([B.HIPCC] + B.FLAGS + B.PER_FILE.get(src, []) + defs + ["-c", os.path.join(csrc, src), "-o", obj],
                        check=True)
         return obj

@@ -2,7 +2,8 @@
 
   python tools/mcmc_bench.py noise   [--rows 600000]
   python tools/mcmc_bench.py sample  [--n 16000000 --num 1600000 --host-n 50000000]
-  python tools/mcmc_bench.py round   [--leaves 1000000]
+  python tools/mcmc_bench.py round   [--leaves 1000000] [--spt-device]
+  python tools/mcmc_bench.py spt     [--leaves 1000000]   host and device SPT build on one hierarchy, one process
 
 Every figure is the median (min-max) of --reps calls after --warmup calls, timed with device events around a call
 that ends in a synchronise where the call itself does not.  One JSON line per measurement."""
@@ -87,6 +88,41 @@ def bench_sample(a):
            **timed(lambda: mcmc.sample_alive(col, num, seed=1), 1, max(3, a.reps // 4)))
 
 
+def bench_spt(a):
+    """The host build and the device build of the SPTs on the same hierarchy (the round's recipe).  The host build
+    takes pageable host tensors, as densify_round hands them over; the device build takes the nodes on the host and
+    the parameter columns as strided views of a packed pinned table (SPTCache.storage), and is also timed on
+    device-resident contiguous columns.  staging: its packing and validation kernels alone (HLGS_SPT_STAGE_PACK)."""
+    from hlgs_core import spt
+    from hlgs_core import synthetic as S
+    sky = 4
+    h = S.make_dynamic_hierarchy(S.make_gaussians(a.leaves, 0, S.make_camera(256, 192), seed=8), skybox_points=sky,
+                                 seed=8)
+    nodes = torch.tensor(h["nodes"])
+    G = int(nodes.shape[0])
+    xyz, scaling = torch.tensor(h["means3D"]), torch.log(torch.tensor(h["scales"]))
+    host = torch.zeros((G, 192), dtype=torch.float32, pin_memory=True)  # SPTCache.host: xyz at word 0, scaling at 7
+    host[:, 0:3] = xyz
+    host[:, 7:10] = scaling
+    vx, vs = host[:, 0:3], host[:, 7:10]
+    args = (sky, a.volume, a.granularity, 256)
+    want = spt.build_hierarchical_spt(nodes, xyz, scaling, *args)
+    got = spt.build_hierarchical_spt_device(nodes, vx, vs, *args)
+    info = dict(spt.last_device_build)
+    for k in ("SPT_starts", "SPT_gaussian_indices", "SPT_root_hierarchy_indices", "upper_tree_nodes"):
+        assert torch.equal(got[k].cpu(), want[k]), k
+    reps = max(3, a.reps // 2)
+    t_host = timed(lambda: spt.build_hierarchical_spt(nodes, xyz, scaling, *args), 1, reps)
+    t_dev = timed(lambda: spt.build_hierarchical_spt_device(nodes, vx, vs, *args), a.warmup, reps)
+    nd, dx, ds = nodes.cuda(), xyz.cuda(), scaling.cuda()
+    t_res = timed(lambda: spt.build_hierarchical_spt_device(nd, dx, ds, *args), a.warmup, reps)
+    t_pack = timed(lambda: spt.build_hierarchical_spt_device(nd, vx, vs, *args, stages=1), a.warmup, reps)
+    t_pack_res = timed(lambda: spt.build_hierarchical_spt_device(nd, dx, ds, *args, stages=1), a.warmup, reps)
+    report("spt_build", rows=G, **info, host=t_host, device_pinned_views=t_dev, device_resident=t_res,
+           staging_pinned_views=t_pack, staging_resident=t_pack_res,
+           device_over_host_min=round(t_dev["min_ms"] / t_host["min_ms"], 4))
+
+
 def bench_round(a):
     from hlgs_core import mcmc, spt
     from hlgs_core import synthetic as S
@@ -130,19 +166,20 @@ def bench_round(a):
     mask &= nodes[:new_size, 2] == 0
     moved = mcmc.relocate_gs(cache.storage, cache.opt_storage, nodes, mask, new_size, sky, seed=1)
     t.append(clock())
-    b = spt.build_hierarchical_spt(nodes[:new_size], cache.storage["xyz"][:new_size],
-                                   cache.storage["scaling"][:new_size], sky, *args.values())
+    build = spt.build_hierarchical_spt_device if a.spt_device else spt.build_hierarchical_spt
+    b = build(nodes[:new_size], cache.storage["xyz"][:new_size], cache.storage["scaling"][:new_size], sky,
+              *args.values())
     t.append(clock())
     cache.reset(b)
     t.append(clock())
     names = ("reset", "spawn", "relocate", "spt_rebuild", "reset_with_spt")
-    report("densify_round", size=size, new_size=new_size, resident_rows=resident, relocated=moved, runs=1,
+    report("densify_round", spt_on_device=bool(a.spt_device), size=size, new_size=new_size, resident_rows=resident, relocated=moved, runs=1,
            **{f"{k}_ms": round(1e3 * (y - x), 2) for k, x, y in zip(names, t, t[1:])})
 
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("what", choices=["noise", "sample", "round"])
+    ap.add_argument("what", choices=["noise", "sample", "round", "spt"])
     ap.add_argument("--rows", type=int, default=600_000)
     ap.add_argument("--n", type=int, default=16_000_000)
     ap.add_argument("--num", type=int, default=1_600_000)
@@ -150,9 +187,10 @@ if __name__ == "__main__":
     ap.add_argument("--leaves", type=int, default=1_000_000)
     ap.add_argument("--volume", type=float, default=0.5)  # config #5 (bench.py): 0.5, 0.00228, 256
     ap.add_argument("--granularity", type=float, default=0.00228)
+    ap.add_argument("--spt-device", action="store_true")  # round: rebuild the SPTs with the device build
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--reps", type=int, default=20)
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("mcmc_bench.py measures on the GPU; none is present")
-    {"noise": bench_noise, "sample": bench_sample, "round": bench_round}[a.what](a)
+    {"noise": bench_noise, "sample": bench_sample, "round": bench_round, "spt": bench_spt}[a.what](a)
