@@ -935,7 +935,7 @@ int hlgs_hier_build(int N, int sh_floats, const float* xyz, const float* shs, co
 // ---------------------------------------------------------------- SPT build on the device (spt_build.hip)
 size_t hlgs_spt_device_scratch_size(int G) { return spt_device_scratch_bytes(G); }
 
-int hlgs_spt_build_device(int G, const int* nodes, const float* xyz, int64_t xyz_stride, const float* log_scales,
+static int spt_build_device_any(bool nary, int G, const int* nodes, const float* xyz, int64_t xyz_stride, const float* log_scales,
                           int64_t scale_stride, int root, float spt_root_volume, float target_granularity,
                           int min_spt_size, void* scratch, int stages, int* sizes, int* host_syncs, void* stream)
 {
@@ -950,14 +950,14 @@ int hlgs_spt_build_device(int G, const int* nodes, const float* xyz, int64_t xyz
     hipStream_t s = (hipStream_t)stream;
     hipGetLastError();
     if (int rc = spt_device_build(G, nodes, xyz, xyz_stride, log_scales, scale_stride, root, spt_root_volume,
-                                  target_granularity, min_spt_size, scratch, stages, sizes, host_syncs, s)) {
+                                  target_granularity, min_spt_size, scratch, stages, sizes, host_syncs, nary, s)) {
         hipGetLastError();
         return rc;
     }
     return check_stage(s, false, "spt_build_device");
 }
 
-int hlgs_spt_emit_device(int G, const int* nodes, void* scratch, int n_spt, int n_entries, int n_upper, int* starts,
+static int spt_emit_device_any(bool nary, int G, const int* nodes, void* scratch, int n_spt, int n_entries, int n_upper, int* starts,
                          float* smax, float* smin, int* gidx, int* roots, int* up_nodes, float* up_xyz,
                          float* up_scaling, float* min_d2, float* radii, void* stream)
 {
@@ -971,9 +971,41 @@ int hlgs_spt_emit_device(int G, const int* nodes, void* scratch, int n_spt, int 
     hipStream_t s = (hipStream_t)stream;
     hipGetLastError();
     if (int rc = spt_device_emit(G, nodes, scratch, n_spt, n_entries, n_upper, starts, smax, smin, gidx, roots,
-                                 up_nodes, up_xyz, up_scaling, min_d2, radii, s))
+                                 up_nodes, up_xyz, up_scaling, min_d2, radii, nary, s))
         return rc;
     return check_stage(s, false, "spt_emit_device");
+}
+
+int hlgs_spt_build_device(int G, const int* nodes, const float* xyz, int64_t xyz_stride, const float* log_scales,
+                          int64_t scale_stride, int root, float spt_root_volume, float target_granularity,
+                          int min_spt_size, void* scratch, int stages, int* sizes, int* host_syncs, void* stream)
+{
+    return spt_build_device_any(false, G, nodes, xyz, xyz_stride, log_scales, scale_stride, root, spt_root_volume,
+                                target_granularity, min_spt_size, scratch, stages, sizes, host_syncs, stream);
+}
+
+int hlgs_spt_build_device_nary(int G, const int* nodes, const float* xyz, int64_t xyz_stride, const float* log_scales,
+                               int64_t scale_stride, int root, float spt_root_volume, float target_granularity,
+                               int min_spt_size, void* scratch, int stages, int* sizes, int* host_syncs, void* stream)
+{
+    return spt_build_device_any(true, G, nodes, xyz, xyz_stride, log_scales, scale_stride, root, spt_root_volume,
+                                target_granularity, min_spt_size, scratch, stages, sizes, host_syncs, stream);
+}
+
+int hlgs_spt_emit_device(int G, const int* nodes, void* scratch, int n_spt, int n_entries, int n_upper, int* starts,
+                         float* smax, float* smin, int* gidx, int* roots, int* up_nodes, float* up_xyz,
+                         float* up_scaling, float* min_d2, float* radii, void* stream)
+{
+    return spt_emit_device_any(false, G, nodes, scratch, n_spt, n_entries, n_upper, starts, smax, smin, gidx, roots,
+                               up_nodes, up_xyz, up_scaling, min_d2, radii, stream);
+}
+
+int hlgs_spt_emit_device_nary(int G, const int* nodes, void* scratch, int n_spt, int n_entries, int n_upper,
+                              int* starts, float* smax, float* smin, int* gidx, int* roots, int* up_nodes,
+                              float* up_xyz, float* up_scaling, float* min_d2, float* radii, void* stream)
+{
+    return spt_emit_device_any(true, G, nodes, scratch, n_spt, n_entries, n_upper, starts, smax, smin, gidx, roots,
+                               up_nodes, up_xyz, up_scaling, min_d2, radii, stream);
 }
 
 // ---------------------------------------------------------------- hierarchy merge (hier_merge.hip)
@@ -1058,7 +1090,7 @@ size_t hlgs_upper_cut_scratch_size(int N)
 static int upper_cut_launch(int N, const int* nodes, const float* xyz, const float* bounds, const float* min_dist2,
                             int nviews, const float* planes, const float* campos, float distance_multiplier,
                             int use_frustum, int use_lod, void* scratch, int* cut, int* count_out, hipStream_t s,
-                            int** count_dev, const void* order = nullptr)
+                            int** count_dev, const void* order = nullptr, bool nary = false)
 {
     if (nviews < 1) return fail(HLGS_ERR_ARG, "n_views < 1");
     if (!nodes || !xyz || !cut || !scratch || (use_frustum && (!bounds || !planes)) ||
@@ -1077,7 +1109,8 @@ static int upper_cut_launch(int N, const int* nodes, const float* xyz, const flo
     a.level_counts = reinterpret_cast<int*>(a.arrive + kCutLevelLaunches);
     a.flat = reinterpret_cast<CutFlat*>(q + align_up(sizeof(CutState) + sizeof(unsigned) * kCutLevelLaunches +
                                                      sizeof(int) * 3 * kCutMaxBlocks));
-    if (order) launch_upper_cut_flat(a, static_cast<const int*>(order), s);
+    if (order) launch_upper_cut_flat(a, static_cast<const int*>(order), s);  // follows no links: either kind of blob
+    else if (nary) launch_upper_cut_nary(a, s);
     else launch_upper_cut(a, s);
     *count_dev = a.count;
     return check_stage(s, false, "upper_tree_cut");
@@ -1113,7 +1146,7 @@ int hlgs_upper_tree_cut_views_device(int N, const int* nodes, const float* xyz, 
                                                     count_device, stream);
 }
 
-int hlgs_upper_tree_cut_views_ordered_device(int N, const int* nodes, const void* order, const float* xyz,
+static int cut_views_ordered_any(bool nary, int N, const int* nodes, const void* order, const float* xyz,
                                              const float* bounds, const float* min_dist2, int n_views,
                                              const float* planes, const float* campos, float distance_multiplier,
                                              int use_frustum, int use_lod, void* scratch, int* cut, int* count_device,
@@ -1128,7 +1161,27 @@ int hlgs_upper_tree_cut_views_ordered_device(int N, const int* nodes, const void
     }
     int* dev = nullptr;
     return upper_cut_launch(N, nodes, xyz, bounds, min_dist2, n_views, planes, campos, distance_multiplier,
-                            use_frustum, use_lod, scratch, cut, count_device, s, &dev, order);
+                            use_frustum, use_lod, scratch, cut, count_device, s, &dev, order, nary);
+}
+
+int hlgs_upper_tree_cut_views_ordered_device(int N, const int* nodes, const void* order, const float* xyz,
+                                             const float* bounds, const float* min_dist2, int n_views,
+                                             const float* planes, const float* campos, float distance_multiplier,
+                                             int use_frustum, int use_lod, void* scratch, int* cut, int* count_device,
+                                             void* stream)
+{
+    return cut_views_ordered_any(false, N, nodes, order, xyz, bounds, min_dist2, n_views, planes, campos,
+                                 distance_multiplier, use_frustum, use_lod, scratch, cut, count_device, stream);
+}
+
+int hlgs_upper_tree_cut_views_ordered_device_nary(int N, const int* nodes, const void* order, const float* xyz,
+                                                  const float* bounds, const float* min_dist2, int n_views,
+                                                  const float* planes, const float* campos,
+                                                  float distance_multiplier, int use_frustum, int use_lod,
+                                                  void* scratch, int* cut, int* count_device, void* stream)
+{
+    return cut_views_ordered_any(true, N, nodes, order, xyz, bounds, min_dist2, n_views, planes, campos,
+                                 distance_multiplier, use_frustum, use_lod, scratch, cut, count_device, stream);
 }
 
 int hlgs_upper_tree_cut_device(int N, const int* nodes, const float* xyz, const float* bounds, const float* min_dist2,

@@ -256,6 +256,7 @@ struct CutArgs {
 };
 size_t upper_cut_state_bytes();
 void launch_upper_cut(const CutArgs& a, hipStream_t s);
+void launch_upper_cut_nary(const CutArgs& a, hipStream_t s);  // child lists, rank-major (hlgs.h)
 void launch_upper_cut_flat(const CutArgs& a, const int* order, hipStream_t s);
 
 // SPT cache bookkeeping of one streaming step (stream.hip, train_post.py:346-430)
@@ -467,10 +468,10 @@ void launch_opacity_reset(int64_t P, int64_t protect, double cap, float* op, flo
 size_t spt_device_scratch_bytes(int G);
 int spt_device_build(int G, const int* nodes, const float* xyz, int64_t xyz_stride, const float* log_scales,
                      int64_t scale_stride, int root, float volume, float tg, int min_size, void* scratch, int stages,
-                     int* sizes, int* syncs, hipStream_t s);
+                     int* sizes, int* syncs, bool nary, hipStream_t s);
 int spt_device_emit(int G, const int* nodes, void* scratch, int n_spt, int n_entries, int n_upper, int* starts,
                      float* smax, float* smin, int* gidx, int* roots, int* up_nodes, float* up_xyz, float* up_scaling,
-                     float* min_d2, float* radii, hipStream_t s);
+                     float* min_d2, float* radii, bool nary, hipStream_t s);
 
 // scan.hip
 void scan_inclusive_u32(const uint32_t* in, uint32_t* out, size_t n, uint32_t* tmp, hipStream_t s);

@@ -19,6 +19,10 @@
 //   upper tree  the upper set is a flag per node, so its sorted order and every searchsorted are one prefix sum.
 //   radii       bottom-up over the links the walks followed: the second child to arrive computes its parent.  Each
 //               parent is a function of its children's final values and max is exact, so the schedule does not show.
+//   n-ary mode  (hlgs_spt_build_device_nary; include/hlgs.h, "the n-ary contract") the same stages over child lists of
+//               child_count members in rank-major order: k_spt_validate_nary in place of the two link checks, the
+//               k_spt_nary_* level step (walk_levels_nary) in place of the two step kernels, k_spt_radii_nary with
+//               child_count arrivals.  The binary kernels and their launches are untouched.
 // Every append is checked against the capacity G, every node may be reached once (a second visit is an error, which
 // ends cycles and shared children), and no kernel follows links in an unbounded loop.
 #include <string>
@@ -32,9 +36,10 @@ int fail_msg(int code, const std::string& msg);  // capi.hip
 namespace {
 
 constexpr int kChildCount = 2, kFirstChild = 3, kNextSibling = 4;
-constexpr uint32_t kErrLink = 1u, kErrTree = 2u, kErrBinary = 4u;
+constexpr uint32_t kErrLink = 1u, kErrTree = 2u, kErrBinary = 4u, kErrCount = 8u, kErrRoot = 16u;
 constexpr uint32_t kSeen = 1u, kExpanded = 2u;
 constexpr int kHdrInts = 64;  // [0] error bits, [1] n_spt, [2] n_entries, [3] n_upper, [4] candidate SPTs
+constexpr int kHdrLevel = 8;  // n-ary walks: [8] children of the level, [9] its longest child list
 
 template <typename T>
 T* take(char*& p, size_t n)
@@ -116,6 +121,7 @@ Bufs carve(void* base, size_t G, size_t* total)
 __device__ __forceinline__ float mx(float a, float b) { return a < b ? b : a; }  // std::max
 
 // ------------------------------------------------------------------------------------------------ staging, validation
+template <bool NARY>
 __global__ void __launch_bounds__(256) k_spt_stage(int G, const int* __restrict__ nodes, const float* __restrict__ xyz,
                                                    int64_t sx, const float* __restrict__ sc, int64_t ss, float tg, Bufs b)
 {
@@ -133,6 +139,7 @@ __global__ void __launch_bounds__(256) k_spt_stage(int G, const int* __restrict_
     b.vol[i] = e[0] * e[1] * e[2];
     b.r3[i] = mx(e[0], mx(e[1], e[2])) * 3.0f;
     b.md[i] = cc == 0 ? -1000000000.f : sqrtf(e[0] * e[1] + e[0] * e[2] + e[1] * e[2]) / tg;
+    if (NARY) return;  // the child lists are checked by k_spt_validate_nary
     if (fc >= G)
         atomicOr((uint32_t*)b.hdr, kErrLink);
     else if (fc >= 0 && (cc != 0 || fc > 0))
@@ -144,6 +151,36 @@ __global__ void __launch_bounds__(256) k_spt_check_sibling(int G, const int* __r
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= G) return;
     if (b.isfirst[i] && nodes[6 * (size_t)i + kNextSibling] >= G) atomicOr((uint32_t*)b.hdr, kErrLink);
+}
+
+// n-ary link validation (hlgs.h, the n-ary contract 1): the thread of a parent walks its list for exactly child_count
+// members; a member must lie in [root, G) (not among the skybox rows), must not be the root, and is claimed once (isfirst, an integer exchange).  After
+// it the rows reachable from the root form a tree, and every list the walks follow ends within child_count links.
+__global__ void __launch_bounds__(256) k_spt_validate_nary(int G, const int* __restrict__ nodes, int root, Bufs b)
+{
+    const int v = blockIdx.x * 256 + threadIdx.x;
+    if (v >= G || v < root) return;  // rows before the root are skybox rows: their node columns are not read
+    const int cc = nodes[6 * (size_t)v + kChildCount];
+    if (cc < 0 || cc >= G) {
+        atomicOr((uint32_t*)b.hdr, kErrCount);
+        return;
+    }
+    int m = nodes[6 * (size_t)v + kFirstChild];
+    for (int r = 0; r < cc; r++) {
+        if (m < root || m >= G) {
+            atomicOr((uint32_t*)b.hdr, kErrLink);
+            return;
+        }
+        if (m == root) {
+            atomicOr((uint32_t*)b.hdr, kErrRoot);
+            return;
+        }
+        if (atomicExch(&b.isfirst[m], 1u)) {
+            atomicOr((uint32_t*)b.hdr, kErrTree);
+            return;
+        }
+        m = nodes[6 * (size_t)m + kNextSibling];
+    }
 }
 
 // ------------------------------------------------------------------------------------------------ upper walk
@@ -234,6 +271,7 @@ __device__ __forceinline__ uint32_t spt_has_children(int G, const int* nodes, co
 }
 
 // T visited entries of the upper walk, fcut scanned into se: candidate k is the k-th inner node of the cut
+template <bool NARY>
 __global__ void __launch_bounds__(256) k_spt_candidates(int G, const int* __restrict__ nodes, int T, Bufs b)
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
@@ -247,9 +285,10 @@ __global__ void __launch_bounds__(256) k_spt_candidates(int G, const int* __rest
     b.e_max[k] = 1000000000000.f;
     b.cnt[k] = 1u;
     b.bsr[k] = __float_as_uint(b.r3[v]);
-    b.eh[k] = spt_has_children(G, nodes, b, v);
+    b.eh[k] = NARY ? 1u : spt_has_children(G, nodes, b, v);  // (an inner node of the cut: child_count != 0)
 }
 
+template <bool NARY = false>
 __device__ __forceinline__ void spt_append(int G, const int* nodes, const Bufs& b, int c, int q, int parent, int k,
                                            float pmin, const float* centre)
 {
@@ -257,7 +296,7 @@ __device__ __forceinline__ void spt_append(int G, const int* nodes, const Bufs& 
     if (atomicExch(&b.seen[c], kSeen))
         atomicOr((uint32_t*)b.hdr, kErrTree);
     else
-        has = spt_has_children(G, nodes, b, c);
+        has = NARY ? (nodes[6 * (size_t)c + kChildCount] > 0 ? 1u : 0u) : spt_has_children(G, nodes, b, c);
     b.lpar[c] = parent;
     const float d0 = b.xyz[3 * (size_t)c] - centre[0], d1 = b.xyz[3 * (size_t)c + 1] - centre[1],
                 d2 = b.xyz[3 * (size_t)c + 2] - centre[2];
@@ -306,6 +345,100 @@ __global__ void __launch_bounds__(256) k_spt_forest_step(int G, const int* __res
     spt_append(G, nodes, b, f, qf, p, k, pmin, centre);
     spt_append(G, nodes, b, s, qs, p, k, pmin, centre);
     atomicAdd(&b.cnt[k], 2u);
+}
+
+// ------------------------------------------------------------------------------------------------ n-ary level step
+// One level of either walk in n-ary mode.  ids = the walk's entry list (front or e_node), flags = its expand flags.
+//   k_spt_nary_counts   w[i] = child_count of an expanding entry, else 0 (ekeep); the longest list (integer atomicMax)
+//   (scan of w, k_spt_nary_tail: the level's children and longest list in two header words, one read-back)
+//   k_spt_nary_scatter  the thread of a parent walks its list for exactly w members and writes them parent-major
+//                       (eincl: child, arrive: the parent's entry), with the rank as a sort key
+//   (a stable radix sort on the rank makes the order rank-major; skipped when every list has one member)
+//   k_spt_nary_upper / k_spt_nary_forest  one thread per child appends it at its rank-major slot
+__global__ void __launch_bounds__(256) k_spt_nary_counts(const int* __restrict__ nodes, int lo, int n,
+                                                         const uint32_t* __restrict__ flags,
+                                                         const int* __restrict__ ids, Bufs b)
+{
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= n) return;
+    const int i = lo + t;
+    const int w = flags[i] ? nodes[6 * (size_t)ids[i] + kChildCount] : 0;
+    b.ekeep[i] = w > 0 ? (uint32_t)w : 0u;
+    if (w > 0) atomicMax(&b.hdr[kHdrLevel + 1], w);
+}
+
+__global__ void k_spt_nary_tail(int last, Bufs b)
+{
+    if (threadIdx.x == 0 && blockIdx.x == 0) b.hdr[kHdrLevel] = (int)b.se[last];
+}
+
+__global__ void __launch_bounds__(256) k_spt_nary_scatter(int G, const int* __restrict__ nodes, int lo, int n, int S,
+                                                          const int* __restrict__ ids, int forest, Bufs b)
+{
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= n) return;
+    const int i = lo + t;
+    const uint32_t w = b.ekeep[i];
+    if (!w) return;
+    const int64_t base = (int64_t)b.se[i] - w;
+    const int p = ids[i];
+    if (base < 0 || base + w > S) {
+        atomicOr((uint32_t*)b.hdr, kErrTree);
+        return;
+    }
+    int m = nodes[6 * (size_t)p + kFirstChild];
+    for (uint32_t r = 0; r < w; r++) {
+        const bool ok = (unsigned)m < (unsigned)G;
+        if (!ok) atomicOr((uint32_t*)b.hdr, kErrLink);  // cannot happen after the validation; stay in range
+        b.eincl[base + r] = ok ? (uint32_t)m : 0u;
+        b.arrive[base + r] = (uint32_t)i;
+        b.keys[base + r] = r;
+        b.vals[base + r] = (uint32_t)(base + r);
+        m = ok ? nodes[6 * (size_t)m + kNextSibling] : 0;
+    }
+    atomicOr(&b.seen[p], kExpanded);
+    if (forest) atomicAdd(&b.cnt[b.e_spt[i]], w);
+}
+
+__global__ void __launch_bounds__(256) k_spt_nary_upper(int G, const int* __restrict__ nodes, int S, int hi,
+                                                        float volume, Bufs b)
+{
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    if (q >= S) return;
+    const uint32_t pm = b.vals[q];
+    if (pm >= (uint32_t)S) {
+        atomicOr((uint32_t*)b.hdr, kErrTree);
+        up_blank(G, b, hi + q);
+        return;
+    }
+    const uint32_t c = b.eincl[pm], i = b.arrive[pm];
+    if (c >= (uint32_t)G || i >= (uint32_t)G) {  // a slot its parent did not write: cannot happen; stay in range
+        atomicOr((uint32_t*)b.hdr, kErrTree);
+        up_blank(G, b, hi + q);
+        return;
+    }
+    up_append(G, nodes, b, (int)c, hi + q, b.front[i], volume);
+}
+
+__global__ void __launch_bounds__(256) k_spt_nary_forest(int G, const int* __restrict__ nodes, int S, int hi, Bufs b)
+{
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    if (q >= S || hi + q >= G) return;
+    const uint32_t pm = b.vals[q];
+    if (pm >= (uint32_t)S) {
+        atomicOr((uint32_t*)b.hdr, kErrTree);
+        spt_blank(G, b, hi + q, 0);
+        return;
+    }
+    const uint32_t c = b.eincl[pm], iu = b.arrive[pm];
+    if (c >= (uint32_t)G || iu >= (uint32_t)G || (uint32_t)b.e_spt[iu] >= (uint32_t)G) {  // cannot happen; stay in range
+        atomicOr((uint32_t*)b.hdr, kErrTree);
+        spt_blank(G, b, hi + q, 0);
+        return;
+    }
+    const int i = (int)iu, k = b.e_spt[i], cn = b.cand[k];
+    const float centre[3] = {b.xyz[3 * (size_t)cn], b.xyz[3 * (size_t)cn + 1], b.xyz[3 * (size_t)cn + 2]};
+    spt_append<true>(G, nodes, b, (int)c, hi + q, b.e_node[i], k, b.e_min[i], centre);
 }
 
 // ------------------------------------------------------------------------------------------------ selection, sort keys
@@ -391,6 +524,7 @@ __device__ __forceinline__ int lower_bound_upper(int G, int U, const Bufs& b, in
     return v < 0 ? 0 : v >= G ? U : (int)(b.upincl[v] - b.up[v]);
 }
 
+template <bool NARY>
 __global__ void __launch_bounds__(256) k_spt_emit_upper(int G, int U, const int* __restrict__ nodes, Bufs b,
                                                         int* up_nodes, float* up_xyz, float* up_scaling)
 {
@@ -408,7 +542,7 @@ __global__ void __launch_bounds__(256) k_spt_emit_upper(int G, int U, const int*
         o[3] = (int)b.numincl[k] - 1;
     } else {
         o[2] = nd[2];
-        o[3] = nd[3] == 0 ? -1 : lower_bound_upper(G, U, b, nd[3]);
+        o[3] = (NARY ? nd[2] == 0 : nd[3] == 0) ? -1 : lower_bound_upper(G, U, b, nd[3]);
     }
     o[4] = nd[4] > 0 ? lower_bound_upper(G, U, b, nd[4]) : nd[4];
     o[5] = v;
@@ -465,6 +599,41 @@ __global__ void __launch_bounds__(256) k_spt_radii(int G, int U, const int* __re
     }
 }
 
+// n-ary: the last of a parent's child_count children to arrive computes it, over the whole list (the max is exact, so
+// the schedule does not show)
+__global__ void __launch_bounds__(256) k_spt_radii_nary(int G, int U, const int* __restrict__ nodes, Bufs b,
+                                                        float* radii)
+{
+    const int v = blockIdx.x * 256 + threadIdx.x;
+    if (v >= G || !b.up[v]) return;
+    const int k = b.sptof[v];
+    if (k < 0 && (b.seen[v] & kExpanded)) return;
+    float r = k >= 0 ? __uint_as_float(b.bsr[k]) : nodes[6 * (size_t)v + kChildCount] == 0 ? b.r3[v] : 0.f;
+    int cur = v;
+    for (int it = 0; it <= U; it++) {
+        __hip_atomic_store(&b.rad[cur], r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const int row = (int)b.upincl[cur] - 1;
+        if (row >= 0 && row < U) radii[row] = r;
+        const int p = b.lpar[cur];
+        if (p < 0 || p >= G || !b.up[p]) return;
+        const int cc = nodes[6 * (size_t)p + kChildCount];
+        if (__hip_atomic_fetch_add(&b.arrive[p], 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) + 1u != (uint32_t)cc)
+            return;
+        const float* pp = b.xyz + 3 * (size_t)p;
+        int m = nodes[6 * (size_t)p + kFirstChild];
+        r = -INFINITY;
+        for (int j = 0; j < cc; j++) {
+            if ((unsigned)m >= (unsigned)G) return;
+            const float rm = __hip_atomic_load(&b.rad[m], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const float* pc = b.xyz + 3 * (size_t)m;
+            const float a0 = pp[0] - pc[0], a1 = pp[1] - pc[1], a2 = pp[2] - pc[2];
+            r = mx(r, rm + sqrtf(a0 * a0 + a1 * a1 + a2 * a2));
+            m = nodes[6 * (size_t)m + kNextSibling];
+        }
+        cur = p;
+    }
+}
+
 #define SPT_TRY(expr)                                                                                   \
     do {                                                                                                \
         hipError_t e_ = (expr);                                                                         \
@@ -484,7 +653,9 @@ int read_back(void* dst, const void* src, size_t bytes, hipStream_t s, int* sync
 
 int error_of(uint32_t bits)
 {
+    if (bits & kErrCount) return fail_msg(HLGS_ERR_ARG, "child_count out of range");
     if (bits & kErrLink) return fail_msg(HLGS_ERR_ARG, "child index out of range");
+    if (bits & kErrRoot) return fail_msg(HLGS_ERR_ARG, "the root is a member of a child list");
     if (bits & kErrBinary) return fail_msg(HLGS_ERR_ARG, "SPT build needs a binary hierarchy");
     if (bits & kErrTree) return fail_msg(HLGS_ERR_ARG, "hierarchy walk does not terminate (a node is reached twice)");
     return HLGS_OK;
@@ -522,9 +693,41 @@ static int walk_levels(int G, uint32_t* flags, const Bufs& b, int first, hipStre
     return HLGS_OK;
 }
 
+// The n-ary form of walk_levels: per level one scan of the expanding entries' list lengths and one read-back (the
+// level's children and its longest list), the parent-major scatter, a stable sort on the rank unless every list has
+// one member, and `append` over the children.
+template <typename Append>
+static int walk_levels_nary(int G, const int* nodes, uint32_t* flags, const int* ids, int forest, const Bufs& b,
+                            int first, hipStream_t s, int* syncs, int* end, Append append)
+{
+    int lo = 0, hi = first;
+    while (hi > lo) {
+        const int n = hi - lo;
+        if (hipMemsetAsync(b.hdr + kHdrLevel, 0, 2 * sizeof(int), s) != hipSuccess)
+            return fail_msg(HLGS_ERR_DEVICE, "SPT build: memset failed");
+        hipLaunchKernelGGL(k_spt_nary_counts, grid((size_t)n), dim3(256), 0, s, nodes, lo, n, flags, ids, b);
+        scan_inclusive_u32(b.ekeep + lo, b.se + lo, (size_t)n, b.scan_tmp, s);
+        hipLaunchKernelGGL(k_spt_nary_tail, dim3(1), dim3(64), 0, s, hi - 1, b);
+        int lev[2] = {0, 0};
+        if (int rc = read_back(lev, b.hdr + kHdrLevel, sizeof(lev), s, syncs)) return rc;
+        const int S = lev[0];
+        if (S == 0) break;
+        if (S < 0 || lev[1] < 1 || (size_t)hi + (size_t)S > (size_t)G)  // more rows than the table holds: not a tree
+            return fail_msg(HLGS_ERR_ARG, "hierarchy walk does not terminate");
+        hipLaunchKernelGGL(k_spt_nary_scatter, grid((size_t)n), dim3(256), 0, s, G, nodes, lo, n, S, ids, forest, b);
+        if (lev[1] > 1)
+            radix_sort_pairs_u32((uint32_t)S, b.keys, b.vals, b.keys_t, b.vals_t, b.hist, b.scan_tmp, s);
+        append(S, hi);
+        lo = hi;
+        hi += S;
+    }
+    *end = hi;
+    return HLGS_OK;
+}
+
 int spt_device_build(int G, const int* nodes, const float* xyz, int64_t xyz_stride, const float* log_scales,
                      int64_t scale_stride, int root, float volume, float tg, int min_size, void* scratch, int stages,
-                     int* sizes, int* syncs, hipStream_t s)
+                     int* sizes, int* syncs, bool nary, hipStream_t s)
 {
     const Bufs b = carve(scratch, (size_t)G, nullptr);
     const size_t g = (size_t)G;
@@ -532,9 +735,15 @@ int spt_device_build(int G, const int* nodes, const float* xyz, int64_t xyz_stri
     if (stages & HLGS_SPT_STAGE_PACK) {
         SPT_TRY(hipMemsetAsync(b.hdr, 0, kHdrInts * sizeof(int), s));
         SPT_TRY(hipMemsetAsync(b.isfirst, 0, g * sizeof(uint32_t), s));
-        hipLaunchKernelGGL(k_spt_stage, grid(g), dim3(256), 0, s, G, nodes, xyz, xyz_stride, log_scales, scale_stride,
-                           tg, b);
-        hipLaunchKernelGGL(k_spt_check_sibling, grid(g), dim3(256), 0, s, G, nodes, b);
+        if (nary) {
+            hipLaunchKernelGGL(k_spt_stage<true>, grid(g), dim3(256), 0, s, G, nodes, xyz, xyz_stride, log_scales,
+                               scale_stride, tg, b);
+            hipLaunchKernelGGL(k_spt_validate_nary, grid(g), dim3(256), 0, s, G, nodes, root, b);
+        } else {
+            hipLaunchKernelGGL(k_spt_stage<false>, grid(g), dim3(256), 0, s, G, nodes, xyz, xyz_stride, log_scales,
+                               scale_stride, tg, b);
+            hipLaunchKernelGGL(k_spt_check_sibling, grid(g), dim3(256), 0, s, G, nodes, b);
+        }
     }
     if (!(stages & HLGS_SPT_STAGE_WALK)) return HLGS_OK;
     // no link is followed before the validation has passed
@@ -546,9 +755,15 @@ int spt_device_build(int G, const int* nodes, const float* xyz, int64_t xyz_stri
     // ---- upper tree and cut
     hipLaunchKernelGGL(k_spt_upper_seed, dim3(1), dim3(64), 0, s, G, nodes, root, volume, b);
     int T = 0;
-    if (int rc = walk_levels(G, b.fe, b, 1, s, syncs, &T, [&](int lo, int n, int H, int hi) {
-            hipLaunchKernelGGL(k_spt_upper_step, grid((size_t)n), dim3(256), 0, s, G, nodes, lo, n, H, hi, volume, b);
-        }))
+    if (nary) {
+        if (int rc = walk_levels_nary(G, nodes, b.fe, b.front, 0, b, 1, s, syncs, &T, [&](int S, int hi) {
+                hipLaunchKernelGGL(k_spt_nary_upper, grid((size_t)S), dim3(256), 0, s, G, nodes, S, hi, volume, b);
+            }))
+            return rc;
+    } else if (int rc = walk_levels(G, b.fe, b, 1, s, syncs, &T, [&](int lo, int n, int H, int hi) {
+                   hipLaunchKernelGGL(k_spt_upper_step, grid((size_t)n), dim3(256), 0, s, G, nodes, lo, n, H, hi,
+                                      volume, b);
+               }))
         return rc;
     scan_inclusive_u32(b.fcut, b.se, (size_t)T, b.scan_tmp, s);
     uint32_t K = 0;
@@ -557,11 +772,19 @@ int spt_device_build(int G, const int* nodes, const float* xyz, int64_t xyz_stri
     // ---- every candidate SPT at once
     int E = 0;
     if (K) {
-        hipLaunchKernelGGL(k_spt_candidates, grid((size_t)T), dim3(256), 0, s, G, nodes, T, b);
-        if (int rc = walk_levels(G, b.eh, b, (int)K, s, syncs, &E, [&](int lo, int n, int H, int hi) {
-                hipLaunchKernelGGL(k_spt_forest_step, grid((size_t)n), dim3(256), 0, s, G, nodes, lo, n, H, hi, b);
-            }))
-            return rc;
+        if (nary) {
+            hipLaunchKernelGGL(k_spt_candidates<true>, grid((size_t)T), dim3(256), 0, s, G, nodes, T, b);
+            if (int rc = walk_levels_nary(G, nodes, b.eh, b.e_node, 1, b, (int)K, s, syncs, &E, [&](int S, int hi) {
+                    hipLaunchKernelGGL(k_spt_nary_forest, grid((size_t)S), dim3(256), 0, s, G, nodes, S, hi, b);
+                }))
+                return rc;
+        } else {
+            hipLaunchKernelGGL(k_spt_candidates<false>, grid((size_t)T), dim3(256), 0, s, G, nodes, T, b);
+            if (int rc = walk_levels(G, b.eh, b, (int)K, s, syncs, &E, [&](int lo, int n, int H, int hi) {
+                    hipLaunchKernelGGL(k_spt_forest_step, grid((size_t)n), dim3(256), 0, s, G, nodes, lo, n, H, hi, b);
+                }))
+                return rc;
+        }
         hipLaunchKernelGGL(k_spt_keep, grid(K), dim3(256), 0, s, (int)K, min_size, b);
         scan_inclusive_u32(b.keep, b.numincl, K, b.scan_tmp, s);
         scan_inclusive_u32(b.cntincl, b.cntincl, K, b.scan_tmp, s);
@@ -591,19 +814,24 @@ int spt_device_build(int G, const int* nodes, const float* xyz, int64_t xyz_stri
 
 int spt_device_emit(int G, const int* nodes, void* scratch, int n_spt, int n_entries, int n_upper, int* starts,
                      float* smax, float* smin, int* gidx, int* roots, int* up_nodes, float* up_xyz, float* up_scaling,
-                     float* min_d2, float* radii, hipStream_t s)
+                     float* min_d2, float* radii, bool nary, hipStream_t s)
 {
     const Bufs b = carve(scratch, (size_t)G, nullptr);
     hipLaunchKernelGGL(k_spt_emit_starts, grid((size_t)G), dim3(256), 0, s, G, n_spt, b, starts, roots);
     if (n_entries)
         hipLaunchKernelGGL(k_spt_emit_entries, grid((size_t)n_entries), dim3(256), 0, s, G, n_entries, b, smax, smin,
                            gidx);
-    hipLaunchKernelGGL(k_spt_emit_upper, grid((size_t)G), dim3(256), 0, s, G, n_upper, nodes, b, up_nodes, up_xyz,
-                       up_scaling);
+    if (nary)
+        hipLaunchKernelGGL(k_spt_emit_upper<true>, grid((size_t)G), dim3(256), 0, s, G, n_upper, nodes, b, up_nodes,
+                           up_xyz, up_scaling);
+    else
+        hipLaunchKernelGGL(k_spt_emit_upper<false>, grid((size_t)G), dim3(256), 0, s, G, n_upper, nodes, b, up_nodes,
+                           up_xyz, up_scaling);
     hipLaunchKernelGGL(k_spt_emit_min_d2, grid((size_t)n_upper), dim3(256), 0, s, G, n_upper, b, up_nodes, min_d2);
     if (radii) {
         SPT_TRY(hipMemsetAsync(b.arrive, 0, (size_t)G * sizeof(uint32_t), s));
-        hipLaunchKernelGGL(k_spt_radii, grid((size_t)G), dim3(256), 0, s, G, n_upper, nodes, b, radii);
+        if (nary) hipLaunchKernelGGL(k_spt_radii_nary, grid((size_t)G), dim3(256), 0, s, G, n_upper, nodes, b, radii);
+        else hipLaunchKernelGGL(k_spt_radii, grid((size_t)G), dim3(256), 0, s, G, n_upper, nodes, b, radii);
     }
     return HLGS_OK;
 }

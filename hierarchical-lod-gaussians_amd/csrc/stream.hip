@@ -335,6 +335,139 @@ void launch_upper_cut(const CutArgs& a, hipStream_t s)
     for (int l = 0; l < kCutLevelLaunches; l++) hipLaunchKernelGGL(k_cut_level, dim3(blocks), dim3(1024), 0, s, a, l);
     hipLaunchKernelGGL(k_upper_cut, dim3(1), dim3(1024), 0, s, a, 1);
 }
+// ---------------------------------------------------------------- n-ary level walk
+// The level walk over child lists (hlgs.h, the n-ary contract): a node's children are child_count rows, first_child and
+// then next_sibling links, and the next frontier is rank-major -- the rank-0 child of every expanding node in frontier
+// order, then the rank-1 children, and so on; on a binary tree that is the order of the walk above.  Every level runs
+// in ONE workgroup, so there is no waiting between workgroups at all: one CU classifies ~160 nodes per us, which
+// bounds this walk (the flat cut serves every upper tree within its limits; this walk serves the rest).
+//   pass 1  cut_count over the thread's run of the frontier, one three-way block scan;
+//   pass 2  the same entries again: the cut's two groups are written, and every expanding node leaves its first child
+//           (a cursor) and its child_count in the free upper halves of the two frontier buffers (a frontier holds at
+//           most N of their 2 N + 2 entries); the longest list and the sum of the counts are reduced in LDS;
+//   ranks   for r = 0 .. longest list - 1: a block scan of (child_count > r) over the expanding nodes places the
+//           rank-r children behind the earlier ranks; each cursor then steps to its next sibling.  A list is walked for
+//           exactly child_count members by the thread that owns its parent, and a link is range-checked before it is
+//           used.  A level costs one block scan per rank of its longest list (~1 us each).
+// The walk ends with the overflow flag for a table that is not a tree: a link out of range, a negative count, more
+// children than rows, or more levels than rows (a cycle of one-child nodes would otherwise never end).
+__device__ __forceinline__ int block_excl1(int v, int* s_w, int* tot)
+{
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    int inc = v;
+    for (int d = 1; d < 64; d <<= 1) {
+        const int x = __shfl_up(inc, d, 64);
+        if (lane >= d) inc += x;
+    }
+    __syncthreads();  // s_w is free
+    if (lane == 63) s_w[w] = inc;
+    __syncthreads();
+    int before = 0, t = 0;
+    for (int k = 0; k < 16; k++) {
+        const int c = s_w[k];
+        if (k < w) before += c;
+        t += c;
+    }
+    *tot = t;
+    return before + inc - v;
+}
+
+__global__ void __launch_bounds__(1024) k_upper_cut_nary(CutArgs a)
+{
+    __shared__ int s_w[16 * 3];
+    __shared__ int s_max, s_bad;
+    __shared__ unsigned long long s_sum;
+    int* const cursor = a.front_a + a.N + 1;  // N + 1 free entries each
+    int* const length = a.front_b + a.N + 1;
+    int size = a.N > 0 ? 1 : 0, total = 0, parity = 0, overflow = 0, levels = 0;
+    if (threadIdx.x == 0) a.front_a[0] = 0;  // root_node = 0
+    __syncthreads();
+    while (size > 0) {
+        if (++levels > a.N) { overflow = 1; break; }
+        const int* front = parity ? a.front_b : a.front_a;
+        int* next = parity ? a.front_a : a.front_b;
+        if (threadIdx.x == 0) {
+            s_max = 0;
+            s_bad = 0;
+            s_sum = 0ull;
+        }
+        const int K = (size + 1023) / 1024;
+        const int i0 = min(size, (int)threadIdx.x * K), i1 = min(size, i0 + K);
+        int3 tot;
+        const int3 o = block_excl3(cut_count(a, front, i0, i1), s_w, &tot);  // (its barriers publish the resets)
+        if (total + tot.x + tot.y > a.capacity || tot.z > a.capacity) { overflow = 1; break; }
+        {
+            int o1 = total + o.x, o2 = total + tot.x + o.y, o3 = o.z, longest = 0, bad = 0;
+            unsigned long long sum = 0ull;
+            for (int b = i0; b < i1; b += kCutBatch) {  // batches of eight whose loads are issued together (cut_write)
+                int v[kCutBatch], st[kCutBatch], kids[kCutBatch], fc[kCutBatch];
+#pragma unroll
+                for (int j = 0; j < kCutBatch; j++) v[j] = b + j < i1 ? front[b + j] : -1;
+#pragma unroll
+                for (int j = 0; j < kCutBatch; j++) {
+                    st[j] = 0;
+                    if (v[j] < 0) continue;
+                    st[j] = cut_node<false>(a, v[j]).st;
+                    kids[j] = a.nodes[6 * v[j] + 2];
+                    fc[j] = a.nodes[6 * v[j] + 3];
+                }
+#pragma unroll
+                for (int j = 0; j < kCutBatch; j++) {
+                    if (st[j] == 1) a.cut[o1++] = v[j];
+                    else if (st[j] == 2) a.cut[o2++] = v[j];
+                    else if (st[j] == 3) {
+                        if (kids[j] < 0) bad = 1;
+                        cursor[o3] = fc[j];
+                        length[o3] = max(kids[j], 0);
+                        o3++;
+                        longest = max(longest, kids[j]);
+                        sum += (unsigned)max(kids[j], 0);
+                    }
+                }
+            }
+            if (longest > 0) atomicMax(&s_max, longest);
+            if (sum) atomicAdd(&s_sum, sum);
+            if (bad) atomicOr(&s_bad, 1);
+        }
+        __syncthreads();  // the expanding nodes' cursors and lengths are visible to the whole workgroup
+        const int longest = s_max;
+        if (s_bad || s_sum > (unsigned long long)a.capacity) { overflow = 1; break; }
+        const int E = tot.z, KE = (E + 1023) / 1024;
+        const int j0 = min(E, (int)threadIdx.x * KE), j1 = min(E, j0 + KE);
+        int base = 0, bad = 0;
+        for (int r = 0; r < longest; r++) {  // (uniform)
+            int c = 0;
+            for (int j = j0; j < j1; j++) c += length[j] > r;
+            int n_r;
+            int q = base + block_excl1(c, s_w, &n_r);
+            for (int j = j0; j < j1; j++) {
+                if (length[j] <= r) continue;
+                const int m = cursor[j];
+                const bool ok = (unsigned)m < (unsigned)a.N;
+                if (!ok) bad = 1;
+                next[q++] = ok ? m : 0;
+                cursor[j] = ok ? a.nodes[6 * m + 4] : 0;
+            }
+            base += n_r;
+        }
+        if (bad) atomicOr(&s_bad, 1);
+        total += tot.x + tot.y;
+        size = base;
+        parity ^= 1;
+        __syncthreads();  // the next frontier is visible to the whole workgroup
+        if (s_bad) { overflow = 1; break; }
+        __syncthreads();  // every thread has read s_bad before the next level resets it
+    }
+    if (threadIdx.x == 0) {
+        a.count[0] = total;
+        a.count[1] = overflow;
+    }
+}
+
+void launch_upper_cut_nary(const CutArgs& a, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_upper_cut_nary, dim3(1), dim3(1024), 0, s, a);
+}
 // ---------------------------------------------------------------- flat coarse cut (round 5)
 // The same cut from the walk order hlgs_upper_tree_order precomputes (see there for why the order is static): the
 // level walk above costs a dependent chain per level (~3 us a narrow level, ~13 us a wide one, 180 us for the 21

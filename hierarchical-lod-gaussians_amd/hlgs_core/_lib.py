@@ -128,6 +128,9 @@ _SIGS = {
                                               _vp]),
     "hlgs_upper_tree_cut_views_ordered_device": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _f, _i, _i, _vp, _vp,
                                                       _vp, _vp]),
+    "hlgs_upper_tree_cut_views_ordered_device_nary": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _f, _i, _i, _vp,
+                                                           _vp, _vp, _vp]),
+    "hlgs_upper_tree_order_nary": (_i, [_i, _vp, _vp]),
     "hlgs_upper_tree_order_size": (_sz, [_i]),
     "hlgs_upper_tree_order": (_i, [_i, _vp, _vp]),
     "hlgs_gather_rows": (_i, [C.c_int64, _i, _vp, _vp, _vp, _vp]),
@@ -143,6 +146,7 @@ _SIGS = {
     "hlgs_activate_reg_backward": (_i, [C.c_int64] + [_vp] * 11),
     "hlgs_adam_step": (_i, [_i, C.POINTER(AdamTensor), C.c_int64, _i, C.c_double, C.c_double, C.c_double, _vp]),
     "hlgs_spt_build": (_i, [_i, _vp, _vp, _vp, _i, _f, _f, _i, _i, C.POINTER(_vp)]),
+    "hlgs_spt_build_nary": (_i, [_i, _vp, _vp, _vp, _i, _f, _f, _i, _i, C.POINTER(_vp)]),
     "hlgs_spt_result_sizes": (_i, [_vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
     "hlgs_spt_result_copy": (_i, [_vp] * 11),
     "hlgs_spt_result_free": (None, [_vp]),
@@ -150,6 +154,9 @@ _SIGS = {
     "hlgs_spt_build_device": (_i, [_i, _vp, _vp, C.c_int64, _vp, C.c_int64, _i, _f, _f, _i, _vp, _i, C.POINTER(_i),
                                    C.POINTER(_i), _vp]),
     "hlgs_spt_emit_device": (_i, [_i, _vp, _vp, _i, _i, _i] + [_vp] * 11),
+    "hlgs_spt_build_device_nary": (_i, [_i, _vp, _vp, C.c_int64, _vp, C.c_int64, _i, _f, _f, _i, _vp, _i,
+                                        C.POINTER(_i), C.POINTER(_i), _vp]),
+    "hlgs_spt_emit_device_nary": (_i, [_i, _vp, _vp, _i, _i, _i] + [_vp] * 11),
     "hlgs_scatter_rows": (_i, [C.c_int64, _i, _vp, _vp, _vp, _vp]),
     "hlgs_ssim_scratch_size": (_sz, [_i, _i, _i]),
     "hlgs_ssim_forward": (_i, [_i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),

@@ -155,9 +155,9 @@ def merge_dynamic_hierarchies(chunks, centers, *, falloff=0.05, root_scale=1e4, 
     write_dynamic_hierarchy, hlgs_core.scene.assemble_hierarchy and the LOD cut (expand_to_size_dynamic,
     get_interpolation_weights_dynamic, interpolate_lod, which go by parent pointers and the parent's child_count and
     so take any child count), and the K chunk roots' ids (int32).  nodes[:, 5] of a kept input-leaf is its rank among
-    the kept input-leaves, -1 elsewhere.  The SPT walk of train_post (cut_hierarchy_on_condition,
-    scene/gaussian_model.py:386-389; hlgs_upper_tree_cut) visits exactly two children per node: it is per chunk and
-    runs before the merge, not on this result.
+    the kept input-leaves, -1 elsewhere.  The reference's SPT walk (cut_hierarchy_on_condition,
+    scene/gaussian_model.py:386-389) visits exactly two children per node and cannot take this result; the SPT path's
+    n-ary mode (hlgs_core.spt.build_hierarchical_spt_device(..., nary=True), then SPTCache) streams it as it is.
 
     Raises ValueError for chunks of different SH width, non-finite centres (a chunk whose root is dropped), a malformed
     node table (an index out of range, a child list shorter than child_count, a child naming another parent, a row in

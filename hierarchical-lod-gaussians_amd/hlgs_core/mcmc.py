@@ -317,6 +317,8 @@ def densify_round(cache, nodes, size, *, cap_max, seed, spt_args, min_opacity=0.
     build_hierarchical_spt_device, which reads nodes[:new_size] and the storage views where they lie (no host copy of
     the parameter columns) and leaves the SPT arrays on the device; otherwise the host build.  Returns the new size."""
     from hlgs_core.spt import build_hierarchical_spt, build_hierarchical_spt_device
+    if getattr(cache, "nary", False):  # select_relocation / apply_relocation assume sibling pairs
+        raise ValueError("densify_round: the MCMC round needs a binary hierarchy; this cache streams an n-ary one")
     size = int(size)
     cache.reset()
     storage, opt_storage = cache.storage, cache.opt_storage

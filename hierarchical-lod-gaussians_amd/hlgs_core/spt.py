@@ -33,24 +33,28 @@ def extract_frustum_planes(view_proj_matrix):
     return planes
 
 
-def upper_tree_order(nodes, device=None):
+def upper_tree_order(nodes, device=None, nary=False):
     """The walk order of an upper tree for the flat coarse cut (hlgs_upper_tree_order, host code): a device int32
     blob, or None when the tree exceeds the flat cut's limits (65,535 nodes on the walk, 64 levels) or is not a tree
-    as the reference walks it -- then the cut walks level by level."""
+    as the reference walks it -- then the cut walks level by level.  nary: the walk follows child lists of child_count
+    members in rank-major order (hlgs.h, the n-ary contract); the flat cut takes either kind of blob."""
     lib = L.load()
     nd = nodes.detach().to("cpu", torch.int32).contiguous()
     N = int(nd.shape[0])
     blob = torch.zeros(((lib.hlgs_upper_tree_order_size(N) + 3) // 4,), dtype=torch.int32)
-    L.check(lib.hlgs_upper_tree_order(N, L.ptr(nd) if N else None, L.ptr(blob)))
+    fn = lib.hlgs_upper_tree_order_nary if nary else lib.hlgs_upper_tree_order
+    L.check(fn(N, L.ptr(nd) if N else None, L.ptr(blob)))
     if not int(blob[2]):
         return None
     return blob.to(device if device is not None else nodes.device)
 
 
 def upper_tree_cut(nodes, xyz, bounds, min_distance_squared, planes, camera_position, distance_multiplier=1.0,
-                   use_frustum=True, use_lod=True, order=None):
+                   use_frustum=True, use_lod=True, order=None, nary=False):
     """Coarse cut of the upper tree from root 0 (int32 device tensor, the reference's order).  order: the blob of
-    upper_tree_order(nodes) for the flat cut (two launches), or None for the level walk; same result."""
+    upper_tree_order(nodes) for the flat cut (two launches), or None for the level walk; same result.  nary: the
+    nodes' children are child lists of child_count members (hlgs.h, the n-ary contract) -- the upper tree of a build
+    with nary=True; planes (n, 4, 4) and camera_position (n, 3) then give the cut of the union of n views."""
     lib = L.load()
     nd = nodes.contiguous().to(torch.int32)
     p = xyz.contiguous().float()
@@ -58,20 +62,26 @@ def upper_tree_cut(nodes, xyz, bounds, min_distance_squared, planes, camera_posi
     b = bounds.contiguous().float() if bounds is not None else None
     md = min_distance_squared.contiguous().float() if min_distance_squared is not None else None
     pl = planes.detach().to(device=dev, dtype=torch.float32).contiguous() if planes is not None else None
-    cam = camera_position.detach().reshape(-1)[:3].to(device=dev, dtype=torch.float32).contiguous()
+    cam = camera_position.detach().reshape(-1)
+    nviews = 1
+    if nary and pl is not None and pl.dim() == 3:
+        nviews = int(pl.shape[0])
+    cam = cam[:3 * nviews].to(device=dev, dtype=torch.float32).contiguous()
     L.require_gpu(nd, p)
     N = nd.size(0)
     cut = torch.empty((max(N, 1),), dtype=torch.int32, device=dev)
     scratch = torch.empty(lib.hlgs_upper_cut_scratch_size(N), dtype=torch.uint8, device=dev)
-    if order is not None:
+    if order is not None or nary:
         cnt = torch.zeros((2,), dtype=torch.int32, device=dev)
-        L.check(lib.hlgs_upper_tree_cut_views_ordered_device(
-            N, L.ptr(nd), L.ptr(order), L.ptr(p), L.ptr(b), L.ptr(md), 1, L.ptr(pl), L.ptr(cam),
-            float(distance_multiplier), int(bool(use_frustum)), int(bool(use_lod)), L.ptr(scratch), L.ptr(cut),
-            L.ptr(cnt), L.stream()))
+        fn = lib.hlgs_upper_tree_cut_views_ordered_device_nary if nary else \
+            lib.hlgs_upper_tree_cut_views_ordered_device
+        L.check(fn(N, L.ptr(nd), L.ptr(order), L.ptr(p), L.ptr(b), L.ptr(md), nviews, L.ptr(pl), L.ptr(cam),
+                   float(distance_multiplier), int(bool(use_frustum)), int(bool(use_lod)), L.ptr(scratch), L.ptr(cut),
+                   L.ptr(cnt), L.stream()))
         n, overflow = (int(v) for v in cnt.cpu())
         if overflow:
-            raise RuntimeError("hlgs: upper-tree cut: the order blob does not fit these nodes")
+            raise RuntimeError("hlgs: upper-tree cut: the order blob does not fit these nodes" if order is not None
+                               else "hlgs: upper-tree cut: the nodes are not a tree of child lists")
         return cut[:n]
     count = C.c_int(0)
     L.check(lib.hlgs_upper_tree_cut(N, L.ptr(nd), L.ptr(p), L.ptr(b), L.ptr(md), L.ptr(pl), L.ptr(cam),
@@ -114,7 +124,7 @@ def scatter_rows(storage, idx, values):
 
 def spt_view_cut(upper_tree_nodes, upper_tree_xyz, bounds, min_distance_squared, view_proj, camera_position,
                  SPT_gaussian_indices, SPT_starts, SPT_max, SPT_min, skybox_points=0, distance_multiplier=1.0,
-                 use_frustum=True, use_lod=False):
+                 use_frustum=True, use_lod=False, nary=False):
     """Body of GaussianModel.get_SPT_cut (gaussian_model.py:108-159) on the HIP path: the coarse cut of the upper
     tree (its LOD condition is disabled there, :124, hence use_lod=False), then the render indices
     [skybox range, get_spt_cut_cuda of the cut's SPT leaves, Gaussians of the cut's non-leaf nodes].
@@ -122,7 +132,7 @@ def spt_view_cut(upper_tree_nodes, upper_tree_xyz, bounds, min_distance_squared,
     import gaussian_hierarchy as GH
     planes = extract_frustum_planes(view_proj) if use_frustum else None
     coarse = upper_tree_cut(upper_tree_nodes, upper_tree_xyz, bounds, min_distance_squared, planes, camera_position,
-                            distance_multiplier, use_frustum, use_lod).long()
+                            distance_multiplier, use_frustum, use_lod, nary=nary).long()
     nodes = upper_tree_nodes
     leaf_mask = nodes[coarse, CHILD_COUNT] == 0
     leaf_nodes = coarse[leaf_mask]
@@ -140,19 +150,21 @@ def spt_view_cut(upper_tree_nodes, upper_tree_xyz, bounds, min_distance_squared,
 
 
 def build_hierarchical_spt(nodes, xyz, scaling, root, SPT_Root_Volume, target_granularity, min_SPT_Size=100,
-                           use_bounding_spheres=True):
+                           use_bounding_spheres=True, nary=False):
     """SPTs and upper tree of a dynamic hierarchy (nodes (G,6) int32, xyz (G,3), scaling (G,3) unactivated
     log-scales).  Returns a dict of CPU tensors: SPT_starts, SPT_max, SPT_min, SPT_gaussian_indices,
     SPT_root_hierarchy_indices, upper_tree_nodes, upper_tree_xyz, upper_tree_scaling, min_distance_squared,
-    bounding_sphere_radii (None without bounding spheres)."""
+    bounding_sphere_radii (None without bounding spheres).  nary=True: the hierarchy's children are child lists of
+    child_count members, as merge_dynamic_hierarchies and create_dynamic_hierarchy write them (hlgs.h, the n-ary
+    contract); the dict then also carries nary=True, which SPTCache and the cuts read."""
     lib = L.load()
     nd = nodes.detach().to("cpu", torch.int32).contiguous()
     p = xyz.detach().to("cpu", torch.float32).contiguous()
     sc = scaling.detach().to("cpu", torch.float32).contiguous()
     h = C.c_void_p()
-    L.check(lib.hlgs_spt_build(nd.size(0), L.ptr(nd), L.ptr(p), L.ptr(sc), int(root), float(SPT_Root_Volume),
-                               float(target_granularity), int(min_SPT_Size), int(bool(use_bounding_spheres)),
-                               C.byref(h)))
+    build = lib.hlgs_spt_build_nary if nary else lib.hlgs_spt_build
+    L.check(build(nd.size(0), L.ptr(nd), L.ptr(p), L.ptr(sc), int(root), float(SPT_Root_Volume),
+                  float(target_granularity), int(min_SPT_Size), int(bool(use_bounding_spheres)), C.byref(h)))
     try:
         ns, ne, nu = C.c_int(), C.c_int(), C.c_int()
         L.check(lib.hlgs_spt_result_sizes(h, C.byref(ns), C.byref(ne), C.byref(nu)))
@@ -169,6 +181,8 @@ def build_hierarchical_spt(nodes, xyz, scaling, root, SPT_Root_Volume, target_gr
         L.check(lib.hlgs_spt_result_copy(h, *[L.ptr(out[k]) if out[k] is not None else None for k in order]))
     finally:
         lib.hlgs_spt_result_free(h)
+    if nary:
+        out["nary"] = True
     return out
 
 
@@ -192,14 +206,16 @@ def _rows3(t, device):
 
 
 def build_hierarchical_spt_device(nodes, xyz, scaling, root, SPT_Root_Volume, target_granularity, min_SPT_Size=100,
-                                  use_bounding_spheres=True, device="cuda", stages=None):
+                                  use_bounding_spheres=True, device="cuda", stages=None, nary=False):
     """build_hierarchical_spt on the GPU (GaussianModel.build_hierarchical_SPT, gaussian_model.py:184-345): the same
     dict, as device tensors (bounding_sphere_radii None without bounding spheres), which SPTCache._set_spt takes as
     it is.  nodes: (G, 6) integer HierarchyNode rows on the device or the host; xyz, scaling: (G, 3) float32 on the
     device or in pinned host memory with any row stride -- the views of SPTCache.storage are read in place -- or in
     pageable host memory, which is copied first.  Raises RuntimeError for a hierarchy the walks cannot follow (a link
     out of range, a node reached twice, a first child without a sibling).  stages: measurement only (a bit mask of
-    hlgs.h's HLGS_SPT_STAGE_*; without the walk stage nothing is returned)."""
+    hlgs.h's HLGS_SPT_STAGE_*; without the walk stage nothing is returned).  nary=True: child lists of child_count
+    members (hlgs.h, the n-ary contract), e.g. the output of merge_dynamic_hierarchies as it is; the dict then also
+    carries nary=True.  last_device_build["host_syncs"] counts the read-backs: O(levels), whatever the list lengths."""
     lib = L.load()
     L.require_gpu()
     dev = torch.device(device)
@@ -215,9 +231,9 @@ def build_hierarchical_spt_device(nodes, xyz, scaling, root, SPT_Root_Volume, ta
     scratch = scratch[-scratch.data_ptr() % 256:]
     sizes, syncs = (C.c_int * 3)(), C.c_int(0)
     st = 3 if stages is None else int(stages)
-    rc = lib.hlgs_spt_build_device(G, L.ptr(nd), L.ptr(p), sp, L.ptr(sc), ss, int(root), float(SPT_Root_Volume),
-                                   float(target_granularity), int(min_SPT_Size), L.ptr(scratch), st, sizes,
-                                   C.byref(syncs), L.stream())
+    build = lib.hlgs_spt_build_device_nary if nary else lib.hlgs_spt_build_device
+    rc = build(G, L.ptr(nd), L.ptr(p), sp, L.ptr(sc), ss, int(root), float(SPT_Root_Volume),
+               float(target_granularity), int(min_SPT_Size), L.ptr(scratch), st, sizes, C.byref(syncs), L.stream())
     ns, ne, nu = (int(v) for v in sizes)
     last_device_build.update(host_syncs=syncs.value, n_spt=ns, n_entries=ne, n_upper=nu)
     L.check(rc)
@@ -229,6 +245,9 @@ def build_hierarchical_spt_device(nodes, xyz, scaling, root, SPT_Root_Volume, ta
                SPT_root_hierarchy_indices=i32(ns), upper_tree_nodes=i32(nu, 6), upper_tree_xyz=f32(nu, 3),
                upper_tree_scaling=f32(nu, 3), min_distance_squared=f32(nu),
                bounding_sphere_radii=f32(nu) if use_bounding_spheres else None)
-    L.check(lib.hlgs_spt_emit_device(G, L.ptr(nd), L.ptr(scratch), ns, ne, nu,
-                                     *[L.ptr(out[k]) if out[k] is not None else None for k in SPT_KEYS], L.stream()))
+    emit = lib.hlgs_spt_emit_device_nary if nary else lib.hlgs_spt_emit_device
+    L.check(emit(G, L.ptr(nd), L.ptr(scratch), ns, ne, nu,
+                 *[L.ptr(out[k]) if out[k] is not None else None for k in SPT_KEYS], L.stream()))
+    if nary:
+        out["nary"] = True
     return out

@@ -202,9 +202,12 @@ class SPTCache:
         """The upper tree, the SPT arrays and the flat cut's walk order of build_hierarchical_spt's dict (the
         constructor, and reset(spt) after a densification round rebuilt them)."""
         dev = self.device
+        # an n-ary build (build_hierarchical_spt(..., nary=True)): the cut walks child lists of child_count members
+        self.nary = bool(spt.get("nary", False))
         self.nodes = spt["upper_tree_nodes"].to(dev, torch.int32).contiguous()
         # the upper tree's walk order for the flat coarse cut (hlgs_upper_tree_order), or None for the level walk
-        self.cut_order = _spt.upper_tree_order(spt["upper_tree_nodes"], dev) if self._flat_cut else None
+        self.cut_order = (_spt.upper_tree_order(spt["upper_tree_nodes"], dev, nary=self.nary) if self._flat_cut
+                          else None)
         self.xyz = spt["upper_tree_xyz"].to(dev, torch.float32).contiguous()
         self.min_distance_squared = spt["min_distance_squared"].to(dev, torch.float32).contiguous()
         if self._use_bounding_spheres:
@@ -328,7 +331,9 @@ class SPTCache:
             self._cut = torch.empty((max(N, 1),), dtype=torch.int32, device=dev)
             self._cut_scratch = torch.empty(lib.hlgs_upper_cut_scratch_size(N), dtype=torch.uint8, device=dev)
             self._cut_count = torch.zeros((2,), dtype=torch.int32, device=dev)
-        L.check(lib.hlgs_upper_tree_cut_views_ordered_device(
+        cut_fn = (lib.hlgs_upper_tree_cut_views_ordered_device_nary if self.nary
+                  else lib.hlgs_upper_tree_cut_views_ordered_device)
+        L.check(cut_fn(
             N, _p(self.nodes), _p(self.cut_order), _p(self.xyz), _p(self.bounds), _p(self.min_distance_squared), G,
             _p(planes), _p(cam), float(distance_multiplier), int(bool(self.use_frustum)), 1, _p(self._cut_scratch),
             _p(self._cut), _p(self._cut_count), L.stream()))

@@ -597,6 +597,62 @@ int hlgs_spt_build_device(int G, const int* nodes, const float* xyz, int64_t xyz
 int hlgs_spt_emit_device(int G, const int* nodes, void* scratch, int n_spt, int n_entries, int n_upper, int* starts,
                          float* smax, float* smin, int* gidx, int* roots, int* up_nodes, float* up_xyz,
                          float* up_scaling, float* min_d2, float* radii, void* stream);
+/* ---- n-ary mode of the SPT path (opt-in; the entry points above stay the binary path, bit for bit) ----
+ * A merged scene hierarchy (hlgs_hier_merge_*) is no binary tree: rows with one child, rows with 3 and more, a root
+ * with K children, and leaves whose first_child column holds id + 1.  The _nary entry points take it as it is.
+ * The n-ary contract:
+ * 1. Child lists.  The children of row v are child_count[v] rows: first_child[v], then next_sibling links.
+ *    child_count == 0 means no children, and first_child is then not read (the merger's rule, see
+ *    hlgs_hier_merge_emit), so the output of the merger and of hlgs_hier_build goes in unchanged.  Every member must
+ *    lie in (root, G) and must be reached once; lists of length 1 are legal.  The rows before the root are the
+ *    skybox rows, which carry no hierarchy: their node columns are not read and they are no members, so with root 0
+ *    the range is the whole table but the root.  A list is walked for
+ *    exactly child_count members, by the thread of its parent.  No kernel follows links in a loop that the table
+ *    itself does not bound, and a link is range-checked before it is used as an index.  The builds validate the whole
+ *    table before any walk; a violation returns HLGS_ERR_ARG.
+ * 2. Walk order: rank-major.  The next frontier is the rank-0 child of every expanding node that has one, in frontier
+ *    order, then the rank-1 child of every expanding node that has one, then rank 2, and so on.  On a binary tree
+ *    this is the reference's cat(first_children, second_children).  This order defines the cut's order, the SPT
+ *    entries' tie order and the flat cut's F*.
+ * 3. The upper walk and the cut classify a node as before: culled, leaf (child_count == 0), condition false, expand.
+ * 4. SPT walk.  It descends below v iff child_count[v] > 0.  Entries as before: max = the parent's min,
+ *    min = min(md(c) + |x_c - centre|, the parent's min); md of a leaf is -1e9 at any level width (the one-element
+ *    branch of get_min_distance, -1e6, depends on the per-SPT walk producing a one-node level and is not
+ *    reproduced).  An SPT is kept if it has more than min_spt_size entries, sorted by max descending with ties in
+ *    walk order; otherwise its entries join the upper tree.
+ * 5. Upper-tree rows are sorted by hierarchy id, parent remapped and row 0's parent -1.  first_child is the SPT
+ *    number at SPT leaves, whose child_count is set to 0; it is -1 where child_count == 0; otherwise it is remapped.
+ *    next_sibling is remapped where it is > 0.  max_side_length is the hierarchy id.  Other rows keep their
+ *    child_count, so the cut can walk their lists.  min_distance_squared as before.
+ * 6. Bounding radii.  A parent's radius is the max over all its children of (child radius + centre distance); the
+ *    last child to arrive computes it.  The max is exact, so the schedule does not show.
+ * 7. Binary equivalence.  On a hierarchy that the binary path accepts, n-ary mode returns the binary path's result
+ *    bit for bit, floats included.
+ * hlgs_spt_build_nary, hlgs_spt_build_device_nary, hlgs_spt_emit_device_nary: arguments, results, scratch and stages
+ *   of their binary neighbours.  The device build reads back once after the validation, once per level of the two
+ *   walks (the level's children and its longest list in one read), once for the candidates and once for the sizes:
+ *   a root with 300 children costs one level, not 300 round trips.
+ * hlgs_upper_tree_order_nary: F* over all ranks, preorder positions and subtree ends of the n-ary tree; the blob
+ *   layout and the limits (65,535 entries, 64 levels) are those of hlgs_upper_tree_order, and the flat cut takes
+ *   either blob (it follows no links).
+ * hlgs_upper_tree_cut_views_ordered_device_nary: hlgs_upper_tree_cut_views_ordered_device over child lists; with
+ *   order = NULL the n-ary level walk, which runs every level in one workgroup (no waiting between workgroups);
+ *   count_device[1] = 1 for a table that is not a tree. */
+int hlgs_spt_build_nary(int G, const int* nodes, const float* xyz, const float* log_scales, int root,
+                        float spt_root_volume, float target_granularity, int min_spt_size, int use_bounding_spheres,
+                        hlgs_spt_result** out);
+int hlgs_spt_build_device_nary(int G, const int* nodes, const float* xyz, int64_t xyz_stride, const float* log_scales,
+                               int64_t scale_stride, int root, float spt_root_volume, float target_granularity,
+                               int min_spt_size, void* scratch, int stages, int* sizes, int* host_syncs, void* stream);
+int hlgs_spt_emit_device_nary(int G, const int* nodes, void* scratch, int n_spt, int n_entries, int n_upper,
+                              int* starts, float* smax, float* smin, int* gidx, int* roots, int* up_nodes,
+                              float* up_xyz, float* up_scaling, float* min_d2, float* radii, void* stream);
+int hlgs_upper_tree_order_nary(int N, const int* nodes_host, void* order_host);
+int hlgs_upper_tree_cut_views_ordered_device_nary(int N, const int* nodes, const void* order, const float* xyz,
+                                                  const float* bounds, const float* min_dist2, int n_views,
+                                                  const float* planes, const float* campos,
+                                                  float distance_multiplier, int use_frustum, int use_lod,
+                                                  void* scratch, int* cut, int* count_device, void* stream);
 /* Row gather dst[i] = src[idx[i]] and scatter dst[idx[i]] = src[i] for n rows of row_bytes (a multiple of 4):
  * the streaming cache's storage[idx].cuda() loads and write-backs (train_post.py:439-488).  src / dst may be
  * pinned host memory (read and written by the GPU over the host link). */

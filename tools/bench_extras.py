@@ -28,6 +28,14 @@
             included (median of 5, host clock), every stage by events, and the bytes the scatter must move (kept rows
             x row bytes, read + write) over its time as a fraction of HBM; beside them the wall time of the recursive
             numpy restatement (tests/hier_merge_ref.py) at 20,011 leaves per chunk.
+  spt_nary  the n-ary SPT path on merge_dynamic_hierarchies' output for K = 4 chunks of 250k rows (hier_merge's
+            recipe, 3 SH floats) beside the binary path on make_dynamic_hierarchy of the same row count:
+            build_hierarchical_spt_device, and one view's coarse cut of the resulting upper tree by the flat cut and
+            by the level walk (host clock around a device synchronise, median of 5 after a warm-up); the volume is
+            the one that 0.5 % of each hierarchy's inner nodes exceed.  The same again with the volume at the first
+            quartile, where no SPT is kept and the whole hierarchy is the upper tree; and the n-ary level walk over
+            a root with 2, 300 and 3,000 leaf children (the cost of a round of its rank loop) and over a chain of
+            299 one-child nodes.
   stream    train_post.py's SPT cache over the same hierarchy: SPT construction (host code), then a camera path
             of views through SPTCache.step (coarse cut, cache bookkeeping, SPT cut, write-back and load of the
             six parameters and twelve Adam moments to and from pinned host storage) and the dense Adam step of
@@ -466,6 +474,117 @@ def bench_hier_merge(sizes=(250_000, 1_000_000, 4_000_000), K=4, shf=48, restate
     return out
 
 
+def bench_spt_nary(rows=250_000, K=4, shf=3, tg=0.02, min_size=64, reps=5):
+    """The n-ary SPT path on the merger's output (K chunks of `rows` rows, the chunk recipe of bench_hier_merge) beside
+    the binary path on make_dynamic_hierarchy of the same row count: the device build, and the per-view coarse cut of
+    the resulting upper tree by the flat cut and by the level walk.  Wall time around a device synchronise, a
+    warm-up, then the median of `reps`."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import hier_merge_ref as MR
+    from hlgs_core import hierarchy as H
+    from hlgs_core import spt
+    cen = MR.centers_for(K)
+
+    def wall(fn, warmup=2):
+        ts = []
+        for _ in range(warmup + reps):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            ts.append((time.perf_counter() - t0) * 1e3)
+        ts = ts[warmup:]
+        return dict(median_ms=round(float(np.median(ts)), 4), min_ms=round(min(ts), 4), max_ms=round(max(ts), 4),
+                    reps=reps)
+
+    g = torch.Generator(device=DEV).manual_seed(rows)
+    u = lambda *sh: torch.rand(*sh, generator=g, device=DEV)  # noqa: E731
+    L = (rows + 1) // 2
+    chunks = [H.build_dynamic_hierarchy(torch.tensor(cen[k], device=DEV) + (u(L, 3) * 2 - 1) * 3.2, u(L, shf) - 0.5,
+                                        u(L) * 0.95 + 0.05, u(L, 3) * 0.05 + 0.005, u(L, 4) - 0.5) for k in range(K)]
+    pos, _, _, ls, _, nodes, _ = H.merge_dynamic_hierarchies(chunks, cen)
+    del chunks
+    G = int(nodes.shape[0])
+    cc = nodes[:, 2]
+    # the volume only the largest 0.5 % of the inner nodes exceed: an upper tree of a few thousand rows over SPTs of a
+    # few hundred entries each
+    quant = lambda nd, sc, q: float(torch.quantile(torch.exp(sc[nd[:, 2] > 0]).prod(1)[:1_000_000], q))  # noqa: E731
+    volume = quant(nodes, ls, 0.995)
+    h = S.make_dynamic_hierarchy(S.make_gaussians((G + 1) // 2, 0, S.make_camera(1920, 1080), seed=0), seed=0)
+    bn = torch.tensor(h["nodes"])
+    bn[:, 3] = torch.where(bn[:, 2] == 2, bn[:, 3], torch.zeros_like(bn[:, 3]))
+    bn, bx, bs = bn.to(DEV), torch.tensor(h["means3D"]).to(DEV), torch.log(torch.tensor(h["scales"])).to(DEV)
+    bvol = quant(bn, bs, 0.995)
+
+    def leg(nd, p, sc, vol, nary):
+        build = lambda: spt.build_hierarchical_spt_device(nd, p, sc, 0, vol, tg, min_size, nary=nary)  # noqa: E731
+        t_build = wall(build)
+        b = build()
+        info = dict(spt.last_device_build)
+        un = b["upper_tree_nodes"]
+        order = spt.upper_tree_order(un, nary=nary)
+        centre = b["upper_tree_xyz"].mean(0).cpu().numpy()
+        cam = S.make_camera(1920, 1080, T=-(centre + np.array([0.0, 0.0, -4.0])))
+        planes = spt.extract_frustum_planes(cam["projmatrix"])
+        args = (un, b["upper_tree_xyz"], b["bounding_sphere_radii"], b["min_distance_squared"], planes, cam["campos"],
+                0.05)
+        out = dict(rows=int(nd.shape[0]), build=t_build, **info)
+        cut = None
+        # (the binary level walk goes through the host-count entry point, the flat cut through the device one)
+        for name, o in (("cut_flat", order), ("cut_level", None)):
+            if name == "cut_flat" and o is None:
+                out[name] = "upper tree beyond the flat cut's limits"
+                continue
+            out[name] = wall(lambda: spt.upper_tree_cut(*args, order=o, nary=nary))
+            c = spt.upper_tree_cut(*args, order=o, nary=nary)
+            assert cut is None or torch.equal(cut, c)
+            cut = c
+        out["cut_nodes"] = int(cut.numel())
+        return out
+
+    # the volume at the first quartile of the inner-node volumes: no SPT reaches min_SPT_Size, the whole hierarchy is
+    # the upper tree (beyond the flat cut's limits) and the level walk runs over all its rows
+    whole = dict(nary=leg(nodes, pos, ls, quant(nodes, ls, 0.25), True),
+                 binary=leg(bn, bx, bs, quant(bn, bs, 0.25), False))
+    assert whole["nary"]["n_spt"] == 0 and whole["nary"]["n_upper"] == G
+
+    # the rank loop of the n-ary level walk: a root with n leaf children is one level whose loop runs n rounds (one block
+    # scan and one dependent next_sibling load each); every inner node expands.  Beside it the 299-deep chain of
+    # one-child nodes (300 levels of one entry).
+    def tree_cut(nd):
+        n = nd.shape[0]
+        g2 = torch.Generator().manual_seed(n)
+        b = spt.build_hierarchical_spt(torch.tensor(nd), torch.randn(n, 3, generator=g2) * 3,
+                                       torch.randn(n, 3, generator=g2) * 0.3 - 2, 0, 0.0, tg, 10, nary=True)
+        d = [b[k].to(DEV) for k in ("upper_tree_nodes", "upper_tree_xyz", "bounding_sphere_radii",
+                                    "min_distance_squared")]
+        cam = torch.tensor([0.5, -0.25, 1.0])
+        cut = lambda: spt.upper_tree_cut(*d, None, cam, 1e-9, use_frustum=False, nary=True)  # noqa: E731
+        return dict(wall(cut), cut_nodes=int(cut().numel()))
+
+    def star(n):
+        nd = np.zeros((n + 1, 6), np.int32)
+        nd[0] = (0, -1, n, 1, 0, 0)
+        for i in range(1, n + 1):
+            nd[i] = (1, 0, 0, i + 1, i + 1 if i < n else 0, 0)
+        return nd
+
+    chain = np.zeros((300, 6), np.int32)
+    for i in range(300):
+        chain[i] = (i, i - 1, 1 if i < 299 else 0, i + 1, 0, 0)
+    rank_loop = {f"star_{n}_children": tree_cut(star(n)) for n in (2, 300, 3000)}
+    rank_loop["chain_299_deep"] = tree_cut(chain)
+    per_rank = (rank_loop["star_3000_children"]["median_ms"] - rank_loop["star_300_children"]["median_ms"]) / 2700
+    rank_loop["us_per_rank"] = round(per_rank * 1e3, 3)
+    return dict(workload=f"merge_dynamic_hierarchies of {K} chunks x {rows} rows -> {G} rows "
+                         f"({int((cc == 1).sum())} one-child rows, {int((cc >= 3).sum())} rows with 3+ children, "
+                         f"longest list {int(cc.max())}); binary: make_dynamic_hierarchy with {int(bn.shape[0])} rows",
+                recipe=dict(target_granularity=tg, min_SPT_Size=min_size, nary_volume=volume, binary_volume=bvol,
+                            cut="one 1920x1080 view 4 units from the upper tree's centroid, distance multiplier 0.05"),
+                nary=leg(nodes, pos, ls, volume, True), binary=leg(bn, bx, bs, bvol, False),
+                whole_hierarchy_as_upper_tree=whole, rank_loop=rank_loop)
+
+
 def bench_stream(P, views=12):
     from hlgs_core import spt
     from hlgs_core.spt_cache import NAMES, SPTCache
@@ -548,6 +667,8 @@ def main():
         out["hier_build"] = bench_hier_build()
     if "hier_merge" in only:
         out["hier_merge"] = bench_hier_merge()
+    if "spt_nary" in only:
+        out["spt_nary"] = bench_spt_nary()
     if "stream" in only:
         out["stream"] = bench_stream(args.P)
     print(json.dumps(out))
