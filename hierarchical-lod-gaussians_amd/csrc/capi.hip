@@ -673,6 +673,50 @@ int hlgs_mcmc_noise(int64_t P, int64_t first_row, float* means3D, const float* o
     return check_stage(s, false, "mcmc_noise");
 }
 
+// ---------------------------------------------------------------- n-ary relocation: the selection (mcmc_nary.hip)
+size_t hlgs_mcmc_select_scratch_size(int size) { return mcmc_select_scratch_bytes(size); }
+
+static int select_args(int size, int sky, const int* nodes, const uint8_t* dead, void* scratch)
+{
+    if (size < 0 || size > HLGS_SPT_MAX_G) return fail(HLGS_ERR_ARG, "size outside [0, HLGS_SPT_MAX_G]");
+    if (sky < 0 || sky > size) return fail(HLGS_ERR_ARG, "sky outside [0, size]");
+    if (size && (!nodes || !dead || !scratch)) return fail(HLGS_ERR_ARG, "missing tensor");
+    if ((uintptr_t)scratch % kAlign) return fail(HLGS_ERR_ARG, "scratch must be 256-byte aligned");
+    return HLGS_OK;
+}
+
+int hlgs_mcmc_select_count(int size, int sky, const int* nodes, const uint8_t* dead, void* scratch, int* counts,
+                           void* stream)
+{
+    if (int rc = select_args(size, sky, nodes, dead, scratch)) return rc;
+    if (!counts) return fail(HLGS_ERR_ARG, "missing counts");
+    hipStream_t s = (hipStream_t)stream;
+    hipGetLastError();
+    if (size == 0) {
+        HLGS_TRY_HIP(hipMemsetAsync(counts, 0, 4 * sizeof(int), s));
+        return HLGS_OK;
+    }
+    size_t bytes = 0;
+    void* zero = mcmc_select_zero_region(scratch, size, &bytes);
+    HLGS_TRY_HIP(hipMemsetAsync(zero, 0, bytes, s));
+    launch_mcmc_select_count(size, sky, nodes, dead, scratch, counts, s);
+    return check_stage(s, false, "mcmc_select_count");
+}
+
+int hlgs_mcmc_select_emit(int size, int sky, const int* nodes, const uint8_t* dead, void* scratch, int* group_parent,
+                          int* group_survivor, int* group_start, int* free_rows, int* alive, void* stream)
+{
+    if (int rc = select_args(size, sky, nodes, dead, scratch)) return rc;
+    if (size == 0) return HLGS_OK;
+    // an empty list has no address; its entries are indexed by the scans of the count, which are then all zero
+    if (!group_start) return fail(HLGS_ERR_ARG, "missing group_start");
+    hipStream_t s = (hipStream_t)stream;
+    hipGetLastError();
+    launch_mcmc_select_emit(size, sky, nodes, dead, scratch, group_parent, group_survivor, group_start, free_rows,
+                            alive, s);
+    return check_stage(s, false, "mcmc_select_emit");
+}
+
 // ---------------------------------------------------------------- adaptive density control (density.hip)
 int hlgs_density_stats(int64_t P, const float* dL_dmean2D, const int* radii, float* grad_accum, float* denom,
                        float* max_radii2D, void* stream)

@@ -447,6 +447,15 @@ void launch_mcmc_noise(int64_t P, int64_t first_row, float* means, const float* 
                        hipStream_t s);
 void launch_rng_fill(int kind, uint64_t seed, uint32_t stream_id, uint64_t first, int64_t n, void* out, hipStream_t s);
 
+// mcmc_nary.hip: the selection of the relocation over child lists (count, read-back by the caller, emit)
+size_t mcmc_select_scratch_bytes(int size);
+void* mcmc_select_zero_region(void* scratch, int size, size_t* bytes);  // what the caller clears before the count
+void launch_mcmc_select_count(int size, int sky, const int* nodes, const uint8_t* dead, void* scratch, int* counts,
+                              hipStream_t s);
+void launch_mcmc_select_emit(int size, int sky, const int* nodes, const uint8_t* dead, void* scratch,
+                             int* group_parent, int* group_survivor, int* group_start, int* free_rows, int* alive,
+                             hipStream_t s);
+
 // density.hip: the adaptive density control of chunk training (statistics, selection, plan, emit, opacity reset)
 void launch_density_stats(int64_t P, const float* g, const int* radii, float* accum, float* denom, float* maxr,
                           hipStream_t s);

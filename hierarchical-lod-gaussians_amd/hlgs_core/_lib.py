@@ -102,6 +102,9 @@ _SIGS = {
     "hlgs_mcmc_sample": (_i, [C.c_int64, _vp, C.c_int64, _vp, C.c_int64, C.c_uint64, C.c_uint32, _vp, _vp, C.c_int64,
                               _vp, _vp]),
     "hlgs_mcmc_noise": (_i, [C.c_int64, C.c_int64, _vp, _vp, _vp, _vp, _vp, C.c_double, C.c_uint64, C.c_uint32, _vp]),
+    "hlgs_mcmc_select_scratch_size": (_sz, [_i]),
+    "hlgs_mcmc_select_count": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "hlgs_mcmc_select_emit": (_i, [_i, _i] + [_vp] * 9),
     "hlgs_density_stats": (_i, [C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "hlgs_density_select": (_i, [C.c_int64, _vp, _vp, _vp, _vp, C.c_double, C.c_double, C.c_double, C.c_int64, _vp,
                                  _vp, _vp]),

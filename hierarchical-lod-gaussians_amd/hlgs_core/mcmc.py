@@ -10,6 +10,9 @@ position noise (:868-878) on the HIP path.
   add_new_gs(...)          GaussianModel.add_new_gs (:1700-1774); its node and row writes are apply_spawn (no GPU)
   relocate_gs(...)         GaussianModel.relocate_gs (:1588-1698); its node and row writes are apply_relocation (no GPU)
   densify_round(...)       the round of train_post.py:710-767 around an SPTCache
+  densify_round_nary(...)  the same round on an n-ary hierarchy (a merged scene): relocate_gs_nary over child lists,
+                           its selection on the GPU (select_relocation_nary, hlgs_mcmc_select_*), its writes
+                           apply_relocation_nary (no GPU); the reference has no counterpart
 
 storage: dict name -> tensor of capacity rows for the names of spt_cache.NAMES (SPTCache.storage, or the tensors of
 GaussianModel.move_storage_to, :430-460); opt_storage: dict name -> {"exp_avgs", "exp_avgs_sqs"}; nodes: capacity x 6
@@ -338,5 +341,198 @@ def densify_round(cache, nodes, size, *, cap_max, seed, spt_args, min_opacity=0.
     else:
         spt = build_hierarchical_spt(nodes[:new_size], storage["xyz"][:new_size], storage["scaling"][:new_size], root,
                                      **args)
+    cache.reset(spt)
+    return new_size
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# The round on an n-ary hierarchy (a merged scene: child lists of any length, include/hlgs.h "n-ary relocation").
+# The entry points above stay the binary path; these stand beside them and, on a hierarchy the binary path accepts,
+# leave its result bit for bit.  add_new_gs and apply_spawn need no n-ary form: they read child_count == 0, overwrite
+# first_child (a merged leaf holds id + 1 there, which nothing reads) and append pairs, which are legal lists.
+def select_relocation_nary(nodes, dead_mask, size, sky, device="cuda"):
+    """The selection of the n-ary relocation (hlgs_mcmc_select_count / _emit, csrc/mcmc_nary.hip): uploads
+    nodes[:size] and the flags, counts, reads the four sizes back (the call's one read-back) and emits.  Returns
+    (group_parent, group_survivor, group_start, free_rows, alive), int32 tensors on the device: per kept group its
+    parent, its promoted survivor (-1 for an unlink group) and its freed rows free_rows[group_start[g] :
+    group_start[g + 1]], groups ascending by first freed row; alive: the respawn candidates, ascending.  A child list
+    that breaks the n-ary contract raises RuntimeError.  With size 0 or no flag set nothing is launched, the table is
+    not read, and every list is empty -- alive too, which then does not mean "no leaves"; flags that select no group
+    still return the candidates."""
+    lib = L.load()
+    L.require_gpu()
+    size, sky = int(size), int(sky)
+    i32 = dict(dtype=torch.int32, device=device)
+    flags = dead_mask[:size].to(torch.uint8)
+    if nodes.shape[0] < size or flags.numel() != size:
+        raise RuntimeError("select_relocation_nary: nodes and dead_mask must hold `size` rows")
+    if size == 0 or not bool(flags.any()):  # nothing to relocate: no launch (relocate_gs returns before it selects)
+        return tuple(torch.zeros(n, **i32) for n in (0, 0, 1, 0, 0))
+    nd = nodes[:size].to(device=device, dtype=torch.int32).contiguous()
+    flags = flags.to(device).contiguous()
+    scratch = torch.empty((lib.hlgs_mcmc_select_scratch_size(size) + 256,), dtype=torch.uint8, device=device)
+    base = scratch[-scratch.data_ptr() % 256:]
+    counts = torch.empty((4,), **i32)
+    L.check(lib.hlgs_mcmc_select_count(size, sky, L.ptr(nd), L.ptr(flags), L.ptr(base), L.ptr(counts), L.stream()))
+    n_groups, n_free, n_alive, status = counts.tolist()
+    if status:
+        raise RuntimeError("select_relocation_nary: a child list breaks the n-ary contract (a link out of range, a "
+                           "list shorter or longer than child_count, or a row in another row's list)")
+    gp, gs = torch.empty((n_groups,), **i32), torch.empty((n_groups,), **i32)
+    start = torch.zeros((n_groups + 1,), **i32)
+    free, alive = torch.empty((n_free,), **i32), torch.empty((n_alive,), **i32)
+    L.check(lib.hlgs_mcmc_select_emit(size, sky, L.ptr(nd), L.ptr(flags), L.ptr(base), L.ptr(gp), L.ptr(gs),
+                                      L.ptr(start), L.ptr(free), L.ptr(alive), L.stream()))
+    return gp, gs, start, free, alive
+
+
+def apply_relocation_nary(nodes, storage, opt_storage, group_parent, group_survivor, group_start, free_rows,
+                          reinit_idx, new_opacity, new_scaling, skybox_points, size):
+    """The writes of the n-ary relocation, no GPU, over the changed rows only; group g (select_relocation_nary's lists,
+    cut to the groups that found a place) respawns at the leaf reinit_idx[g], whose relocated opacity and scale are
+    new_opacity[g], new_scaling[g].  In this order: (1) every dead member takes the parameters of its group's place;
+    (2) unlink groups: the parent's list is rewritten to its survivors in their old order -- before the promotions,
+    because an unlink parent can be the survivor of a promote group one level up; (3) promote groups, deepest survivor
+    first (:1641-1664): the parent takes the survivor's six rows, child_count and first_child, and every child of the
+    survivor its new parent and depth (A-26, A-29 as in apply_relocation); (4) the place becomes the parent of the
+    group's freed rows, chained in order; (5) a promoted survivor's row is a copy of the group's first freed row
+    (A-25) with zeroed moments.  On a binary hierarchy this is apply_relocation, statement for statement."""
+    re = reinit_idx.to("cpu", torch.int64)
+    n = int(re.numel())
+    if n == 0:
+        return
+    if n > int(group_parent.numel()):
+        raise RuntimeError("apply_relocation_nary: more respawn places than groups")
+    # the first n groups are placed; longer lists (fewer places than groups) are cut here
+    gp = group_parent.to("cpu", torch.int64)[:n]
+    gs = group_survivor.to("cpu", torch.int64)[:n]
+    st = group_start.to("cpu", torch.int64)[:n + 1]
+    fr = free_rows.to("cpu", torch.int64)[:int(st[n])]
+    m = st[1:n + 1] - st[:n]
+    promote = gs >= 0
+    k = m - promote.long()
+    gid = torch.repeat_interleave(torch.arange(n), m)
+    pos = torch.arange(int(fr.numel())) - st[gid]
+    is_dead = pos < k[gid]  # in a promote group the last freed row is the survivor
+    dead, dead_re = fr[is_dead], re[gid[is_dead]]
+    s = storage
+    s["xyz"][dead] = s["xyz"][dead_re]
+    s["f_dc"][dead] = s["f_dc"][dead_re]
+    s["f_rest"][dead] = s["f_rest"][dead_re]
+    s["rotation"][dead] = s["rotation"][dead_re]
+    s["opacity"][dead] = new_opacity.to("cpu")[gid[is_dead]]
+    s["scaling"][dead] = new_scaling.to("cpu")[gid[is_dead]]
+    # unlink groups: the parent keeps its survivors, in their old order (one pass per rank of the longest list)
+    up = gp[~promote]
+    if up.numel():
+        cc = nodes[up, CHILD_COUNT].long()
+        cur = nodes[up, FIRST_CHILD].long()
+        prev = torch.full_like(cur, -1)
+        for j in range(int(cc.max())):
+            act = j < cc
+            keep = act & ~torch.isin(cur, dead)
+            head, link = keep & (prev < 0), keep & (prev >= 0)
+            nodes[up[head], FIRST_CHILD] = cur[head].to(torch.int32)
+            nodes[prev[link], NEXT_SIBLING] = cur[link].to(torch.int32)
+            prev = torch.where(keep, cur, prev)
+            cur = torch.where(act, nodes[cur, NEXT_SIBLING].long(), cur)
+        nodes[prev, NEXT_SIBLING] = 0
+        nodes[up, CHILD_COUNT] = (cc - k[~promote]).to(torch.int32)
+    # promote groups: the survivor moves into the parent (:1641-1664), deepest first
+    sv, pv = gs[promote], gp[promote]
+    for depth in range(int(torch.max(nodes[skybox_points:size, DEPTH])) if sv.numel() else 0, 0, -1):
+        lv = nodes[sv, DEPTH] == depth
+        sd, pd = sv[lv], pv[lv]
+        for name in NAMES:
+            s[name][pd] = s[name][sd]
+        nodes[pd, CHILD_COUNT] = nodes[sd, CHILD_COUNT]
+        nodes[pd, FIRST_CHILD] = nodes[sd, FIRST_CHILD]
+        # the survivor's children move up, the whole list; a leaf survivor has none (A-26)
+        inner = nodes[sd, CHILD_COUNT] > 0
+        sd, pd = sd[inner], pd[inner]
+        if sd.numel() == 0:
+            continue
+        cc = nodes[sd, CHILD_COUNT].long()
+        cur = nodes[sd, FIRST_CHILD].long()
+        for j in range(int(cc.max())):
+            act = j < cc
+            ca, pa = cur[act], pd[act]
+            nodes[ca, PARENT] = pa.to(torch.int32)
+            nodes[ca, DEPTH] = nodes[pa, DEPTH] + 1
+            cur = torch.where(act, nodes[cur, NEXT_SIBLING].long(), cur)
+    # the respawn leaves become the parents of their groups' freed rows (:1667-1682)
+    nodes[re, CHILD_COUNT] = m.to(torch.int32)
+    nodes[re, FIRST_CHILD] = fr[st[:n]].to(torch.int32)
+    place = re[gid]
+    nxt = torch.zeros_like(fr)
+    nxt[:-1] = fr[1:]
+    nxt[pos == m[gid] - 1] = 0
+    nodes[fr, DEPTH] = nodes[place, DEPTH] + 1
+    nodes[fr, PARENT] = place.to(torch.int32)
+    nodes[fr, CHILD_COUNT] = 0
+    nodes[fr, FIRST_CHILD] = 0
+    nodes[fr, NEXT_SIBLING] = nxt.to(torch.int32)
+    # a promoted survivor's row is a copy of the first freed row (:1684-1689: xyz, opacity, f_dc, scaling)
+    first = fr[st[:n]][promote]
+    for name in ("xyz", "opacity", "f_dc", "scaling"):
+        s[name][sv] = s[name][first]
+    for name in NAMES:
+        opt_storage[name]["exp_avgs"][sv] = 0
+        opt_storage[name]["exp_avgs_sqs"][sv] = 0
+
+
+def relocate_gs_nary(storage, opt_storage, nodes, dead_mask, size, skybox_points, *, seed, device="cuda"):
+    """relocate_gs on an n-ary hierarchy: the groups of select_relocation_nary respawn as the children of leaves drawn
+    by opacity, one place per group (2 n_groups draws on STREAM_RELOCATE, unique, the seeded permutation; with fewer
+    places than groups the first len(places) groups are kept).  Returns the number of dead Gaussians relocated.  On a
+    binary hierarchy the state and the count are relocate_gs's, bit for bit."""
+    size = int(size)
+    dead_mask = dead_mask.to("cpu")
+    if int(dead_mask.sum()) == 0:
+        return 0
+    gp, gs, start, free, alive = select_relocation_nary(nodes, dead_mask, size, skybox_points, device)
+    n_groups = int(gp.numel())
+    if n_groups == 0:  # flags on rows that are no candidates, or only single dead children of wide lists
+        return 0
+    # the candidates stay on the device: they are the one list of the selection that scales with the scene
+    reinit, counts = sample_alive(_opacity_column(storage, size, device), 2 * n_groups, alive, seed=seed,
+                                  stream=STREAM_RELOCATE, size=size, device=device)
+    reinit = reinit.unique().cpu().long()
+    g = torch.Generator()
+    g.manual_seed(int(seed) & 0x7fffffffffffffff)
+    reinit = reinit[torch.randperm(len(reinit), generator=g)[:n_groups]]
+    n = min(n_groups, len(reinit))  # fewer distinct respawn places than groups (:1622-1625)
+    gp, gs, start = gp[:n].cpu(), gs[:n].cpu(), start[:n + 1].cpu()
+    _, _, _, new_opacity, new_scaling, _ = update_params(storage, reinit, counts, device)
+    apply_relocation_nary(nodes, storage, opt_storage, gp, gs, start, free.cpu(), reinit, new_opacity, new_scaling,
+                          skybox_points, size)
+    return int(start[n]) - int((gs >= 0).sum())
+
+
+def densify_round_nary(cache, nodes, size, *, cap_max, seed, spt_args, min_opacity=0.005, device="cuda",
+                       spt_on_device=False):
+    """densify_round for a cache over an n-ary hierarchy (a merged scene), with the same arguments and sequence: the
+    cache is emptied, leaves are spawned (add_new_gs as it is: it reads child_count == 0 and appends pairs), the
+    leaves at or below min_opacity before the spawn are relocated by relocate_gs_nary, the SPTs are rebuilt with the
+    n-ary build when the cache streams an n-ary hierarchy, and handed to the cache.  A binary cache is accepted too:
+    the round is then densify_round's, bit for bit.  Returns the new size."""
+    from hlgs_core.spt import build_hierarchical_spt, build_hierarchical_spt_device
+    size = int(size)
+    nary = bool(getattr(cache, "nary", False))
+    cache.reset()
+    storage, opt_storage = cache.storage, cache.opt_storage
+    threshold = _inverse_sigmoid(torch.tensor(min_opacity)).item()
+    dead_indices = torch.where(storage["opacity"][:size, 0] <= threshold)[0]
+    new_size = add_new_gs(storage, nodes, size, cap_max, seed=seed, device=device)
+    dead_mask = torch.zeros(new_size, dtype=torch.bool)
+    dead_mask[dead_indices] = True
+    dead_mask = torch.logical_and(dead_mask, nodes[:new_size, CHILD_COUNT] == 0)
+    relocate_gs_nary(storage, opt_storage, nodes, dead_mask, new_size, cache.sky, seed=seed, device=device)
+    args = dict(spt_args)
+    root = args.pop("root", cache.sky)
+    build = build_hierarchical_spt_device if spt_on_device else build_hierarchical_spt
+    if spt_on_device:
+        args["device"] = device
+    spt = build(nodes[:new_size], storage["xyz"][:new_size], storage["scaling"][:new_size], root, **args, nary=nary)
     cache.reset(spt)
     return new_size

@@ -653,6 +653,42 @@ int hlgs_upper_tree_cut_views_ordered_device_nary(int N, const int* nodes, const
                                                   const float* planes, const float* campos,
                                                   float distance_multiplier, int use_frustum, int use_lod,
                                                   void* scratch, int* cut, int* count_device, void* stream);
+/* ---- n-ary relocation: the selection of the MCMC round on child lists (opt-in; relocate_gs's pair selection stays
+ *      as it is) ----
+ * GaussianModel.relocate_gs (scene/gaussian_model.py:1588-1698) is defined on sibling pairs only.  On the hierarchies of
+ * the n-ary contract above the selection follows these rules, chosen so that on a hierarchy the binary path accepts
+ * they give its selection (contract 7's analogue).  dead: size bytes, non-zero = flagged.
+ *   candidate   a row v > sky with child_count 0 that is flagged (the root and inner rows are never candidates; the
+ *               rows below sky are not read).
+ *   group       per parent p with c children of which k are candidates, in list order.  k == c: the last member stops
+ *               being a candidate (:1597-1599), so k = c - 1.  a = c - k survivors.  a == 1: a promote group -- the
+ *               survivor s moves into p, and the freed rows are the k dead members in list order, then s (m = k + 1).
+ *               a >= 2: an unlink group -- the freed rows are the k dead members in list order (m = k), survivor -1.
+ *               Groups with k == 0 or m < 2 are dropped: a single dead child of three or more waits.
+ *   order       kept groups ascending by their first freed row; on a binary tree the ascending dead list of
+ *               relocate_gs, with (dead, sibling) as the freed pair.
+ *   alive       rows >= sky with child_count 0 that are not flagged and are not the survivor of a kept promote group,
+ *               ascending: the respawn candidates.
+ * hlgs_mcmc_select_scratch_size(size): bytes of device scratch (256-byte aligned) both calls take.
+ * hlgs_mcmc_select_count: nodes size x 6 int32 and dead in device memory.  Every row with child_count > 0 walks its own
+ *   list for child_count members.  Validation, before a link is used as an index: child_count in [0, size); every member
+ *   in (sky, size) and naming the walking row as its parent (so no row is in two lists); the last member's next_sibling
+ *   0.  A violation sets HLGS_MCMC_SELECT_STATUS_LINKS and the list is not followed.  counts (4 device int32, valid once
+ *   the stream has passed the call -- the selection's one read-back, by the caller): {groups, freed rows, alive,
+ *   status}; with a non-zero status the three sizes are 0.
+ * hlgs_mcmc_select_emit: nodes, dead and scratch as given to the count, unchanged in between.  group_parent and
+ *   group_survivor (groups), group_start (groups + 1: group g's freed rows are free_rows[group_start[g] ..
+ *   group_start[g + 1])), free_rows (freed rows) and alive (alive), caller-allocated device int32 arrays sized from
+ *   counts.  With a non-zero status its kernel does nothing.
+ * size in [0, HLGS_SPT_MAX_G], sky in [0, size], else HLGS_ERR_ARG.  Nothing is allocated, no host synchronisation,
+ * every launch goes to `stream`.  A list is walked by one thread.  The result does not depend on the launch shape:
+ * integers only, every word written by one thread, the status an OR. */
+#define HLGS_MCMC_SELECT_STATUS_LINKS 1u
+size_t hlgs_mcmc_select_scratch_size(int size);
+int hlgs_mcmc_select_count(int size, int sky, const int* nodes, const uint8_t* dead, void* scratch, int* counts,
+                           void* stream);
+int hlgs_mcmc_select_emit(int size, int sky, const int* nodes, const uint8_t* dead, void* scratch, int* group_parent,
+                          int* group_survivor, int* group_start, int* free_rows, int* alive, void* stream);
 /* Row gather dst[i] = src[idx[i]] and scatter dst[idx[i]] = src[i] for n rows of row_bytes (a multiple of 4):
  * the streaming cache's storage[idx].cuda() loads and write-backs (train_post.py:439-488).  src / dst may be
  * pinned host memory (read and written by the GPU over the host link). */

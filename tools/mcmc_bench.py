@@ -4,6 +4,8 @@
   python tools/mcmc_bench.py sample  [--n 16000000 --num 1600000 --host-n 50000000]
   python tools/mcmc_bench.py round   [--leaves 1000000] [--spt-device]
   python tools/mcmc_bench.py spt     [--leaves 1000000]   host and device SPT build on one hierarchy, one process
+  python tools/mcmc_bench.py select  [--leaves 1000000 --merged-rows 250000 --out FILE]   the relocation's selection:
+                                     host (binary) against device (child lists), and the device on a merged K = 4 scene
 
 Every figure is the median (min-max) of --reps calls after --warmup calls, timed with device events around a call
 that ends in a synchronise where the call itself does not.  One JSON line per measurement."""
@@ -177,9 +179,88 @@ def bench_round(a):
            **{f"{k}_ms": round(1e3 * (y - x), 2) for k, x, y in zip(names, t, t[1:])})
 
 
+def bench_select(a):
+    """The selection of the relocation: the device selection over child lists (select_relocation_nary: the upload of
+    the node table and the flags, the count, its read-back, the emit, and the read-back of the group lists; the alive
+    list stays on the device, where the sampler reads it) beside the host selection of the binary round
+    (select_relocation: nonzero and isin over every row) on the binary scene of `round` with 5 % dead leaves, and the
+    device selection on the merged K = 4 scene of tools/bench_extras.py's spt_nary.  Wall time around a synchronise."""
+    import hier_merge_ref as MR
+    from hlgs_core import hierarchy as H
+    from hlgs_core import mcmc
+    from hlgs_core import synthetic as S
+
+    def wall(fn):
+        ts = []
+        for _ in range(a.warmup + a.reps):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            ts.append((time.perf_counter() - t0) * 1e3)
+        ts = sorted(ts[a.warmup:])
+        return dict(median_ms=round(ts[len(ts) // 2], 4), min_ms=round(ts[0], 4), max_ms=round(ts[-1], 4), reps=a.reps)
+
+    def flags(nodes, sky):
+        rng = np.random.default_rng(8)
+        leaves = torch.where(nodes[sky:, 2] == 0)[0] + sky
+        mask = torch.zeros(nodes.shape[0], dtype=torch.bool)
+        mask[leaves[torch.tensor(rng.choice(len(leaves), size=len(leaves) // 20, replace=False))]] = True
+        return mask
+
+    def device_select(nodes, mask, sky):
+        out = mcmc.select_relocation_nary(nodes, mask, nodes.shape[0], sky)
+        return tuple(t.cpu() for t in out[:4]) + (out[4],)
+
+    results = {}
+    sky = 4
+    print(f"select: building the binary scene of {a.leaves} leaves", file=sys.stderr, flush=True)
+    h = S.make_dynamic_hierarchy(S.make_gaussians(a.leaves, 0, S.make_camera(256, 192), seed=8), skybox_points=sky,
+                                 seed=8)
+    nodes = torch.tensor(h["nodes"])
+    mask = flags(nodes, sky)
+    size = int(nodes.shape[0])
+    dead, sib, alive = mcmc.select_relocation(nodes, mask, size)
+    gp, gs, st, fr, al = device_select(nodes, mask, sky)
+    assert torch.equal(fr.long(), torch.stack([dead, sib.long()], 1).reshape(-1)) and torch.equal(gs, sib)
+    assert torch.equal(al.cpu().long(), alive) and torch.equal(gp, nodes[dead, 1])
+    results["binary"] = dict(rows=size, dead_flags=int(mask.sum()), groups=int(gp.numel()), alive=int(al.numel()),
+                             host_select_relocation=wall(lambda: mcmc.select_relocation(nodes, mask, size)),
+                             device_select_relocation_nary=wall(lambda: device_select(nodes, mask, sky)))
+    b = results["binary"]
+    b["device_over_host_median"] = round(b["device_select_relocation_nary"]["median_ms"] /
+                                         b["host_select_relocation"]["median_ms"], 4)
+    report("select_binary", **b)
+    # the merged scene of bench_extras.bench_spt_nary: K = 4 chunks of 250,000 rows
+    K, rows, shf = 4, a.merged_rows, 3
+    cen = MR.centers_for(K)
+    g = torch.Generator(device="cuda").manual_seed(rows)
+    u = lambda *sh: torch.rand(*sh, generator=g, device="cuda")  # noqa: E731
+    L = (rows + 1) // 2
+    chunks = [H.build_dynamic_hierarchy(torch.tensor(cen[k], device="cuda") + (u(L, 3) * 2 - 1) * 3.2, u(L, shf) - 0.5,
+                                        u(L) * 0.95 + 0.05, u(L, 3) * 0.05 + 0.005, u(L, 4) - 0.5) for k in range(K)]
+    nodes = H.merge_dynamic_hierarchies(chunks, cen)[5].cpu()
+    del chunks
+    mask = flags(nodes, 0)
+    gp, gs, st, fr, al = device_select(nodes, mask, 0)
+    results["merged_k4"] = dict(rows=int(nodes.shape[0]), longest_list=int(nodes[:, 2].max()),
+                                dead_flags=int(mask.sum()), groups=int(gp.numel()),
+                                promote_groups=int((gs >= 0).sum()), freed_rows=int(fr.numel()),
+                                alive=int(al.numel()),
+                                device_select_relocation_nary=wall(lambda: device_select(nodes, mask, 0)))
+    report("select_merged_k4", **results["merged_k4"])
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(dict(measurement="mcmc_select", warmup=a.warmup, **results), f, indent=1)
+            f.write("\n")
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("what", choices=["noise", "sample", "round", "spt"])
+    ap.add_argument("what", choices=["noise", "sample", "round", "spt", "select"])
+    ap.add_argument("--merged-rows", type=int, default=250_000)  # select: rows per chunk of the merged K = 4 scene
+    ap.add_argument("--out", default=None)  # select: also write the results to this JSON file
     ap.add_argument("--rows", type=int, default=600_000)
     ap.add_argument("--n", type=int, default=16_000_000)
     ap.add_argument("--num", type=int, default=1_600_000)
@@ -193,4 +274,5 @@ if __name__ == "__main__":
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("mcmc_bench.py measures on the GPU; none is present")
-    {"noise": bench_noise, "sample": bench_sample, "round": bench_round, "spt": bench_spt}[a.what](a)
+    {"noise": bench_noise, "sample": bench_sample, "round": bench_round, "spt": bench_spt,
+     "select": bench_select}[a.what](a)
