@@ -865,8 +865,13 @@ void launch_rows_packed(int T, float* const* tabs, const int* words, int64_t n, 
 
 // Compaction inside device memory (dst_rows = identity, every table device-only): dst_t[i] = src_t[src_rows[i]].
 // Lane = one 16-byte chunk of the destination (aligned store).  Its four source words lie in rows r .. r_end; when
-// those rows are consecutive in the source too (src_rows[r_end] - src_rows[r] = r_end - r, which holds inside the
-// long runs of kept rows) they are one contiguous 16-byte load at 4-byte alignment, otherwise four word loads.
+// every adjacent pair of those rows is consecutive in the source too (which holds inside the long runs of kept rows)
+// they are one contiguous 16-byte load at 4-byte alignment, otherwise four word loads.  src_rows may be in any order
+// and may repeat, so the end rows alone (src_rows[r_end] - src_rows[r] = r_end - r) decide only a chunk without
+// interior rows: chunks start at multiples of four words, so a chunk of rows of two words or more is r, r + 1 at
+// most (two whole rows for 2-word rows), and only 1-word rows, four to a chunk, have their two interior rows looked
+// up as well (tests/test_row_cases_cpu.py enumerates the spans).  A strictly increasing list passes both tests or
+// neither, and takes the 16-byte load wherever the end rows alone allowed it.
 // Round 6: one 1-D grid over every table's chunks -- block b copies kCompactChunks consecutive chunks of one table
 // (CompactTabs::bstart, the blocks of the tables before it) -- instead of a 2-D grid of 2,048 blocks per table, in which
 // the narrow tables (opacity, 3-float rows: a few hundred blocks of work) left most of their blocks idle and the wide
@@ -906,18 +911,24 @@ __global__ void __launch_bounds__(256) k_rows_compact(CompactTabs tabs, int T, i
         }
     }
     int s0[kCompactU], s1[kCompactU];
+    bool run[kCompactU];  // the chunk's interior rows continue the run from s0 (1-word rows: rows r + 1 and r + 2)
 #pragma unroll
     for (int u = 0; u < kCompactU; u++) {
         const bool in = w0 + u * 1024 < total;
         s0[u] = in ? src_rows[rr[u]] : 0;
         s1[u] = in ? src_rows[min(re[u], n - 1)] : 0;
+        run[u] = true;
+        if (words == 1 && in) {  // uniform over the block
+            const int m1 = src_rows[min(rr[u] + 1, n - 1)], m2 = src_rows[min(rr[u] + 2, n - 1)];
+            run[u] = m1 - s0[u] == 1 && m2 - s0[u] == 2;
+        }
     }
     uint4 v[kCompactU];
     bool fast[kCompactU];
 #pragma unroll
     for (int u = 0; u < kCompactU; u++) {
         const int64_t wu = w0 + u * 1024;
-        fast[u] = wu + 4 <= total && s1[u] - s0[u] == re[u] - rr[u];
+        fast[u] = wu + 4 <= total && run[u] && s1[u] - s0[u] == re[u] - rr[u];
         if (fast[u]) v[u] = *reinterpret_cast<const uint4_a4*>(src + (int64_t)s0[u] * words + kk[u]);
     }
 #pragma unroll
@@ -939,8 +950,11 @@ __global__ void __launch_bounds__(256) k_rows_compact(CompactTabs tabs, int T, i
 void launch_rows_multi(int T, const RowCopy* tabs, int64_t n, const int* src_rows, const int* dst_rows, hipStream_t s)
 {
     bool compact = src_rows && !dst_rows && T <= kCompactTables;
+    // a table of 0-byte rows has no chunk and no block (bstart[t] = bstart[t + 1]) whatever its pointers are -- callers
+    // pass NULL for an empty tensor -- so it does not take the other tables of the call off this path
     for (int t = 0; t < T && compact; t++)
-        compact = tabs[t].device_only && (reinterpret_cast<uintptr_t>(tabs[t].dst) & 15u) == 0;
+        compact = tabs[t].row_bytes == 0 ||
+                  (tabs[t].device_only && (reinterpret_cast<uintptr_t>(tabs[t].dst) & 15u) == 0);
     if (compact) {
         CompactTabs ct{};
         int64_t blocks = 0;

@@ -739,7 +739,8 @@ typedef struct hlgs_cache_plan {
 size_t hlgs_spt_cache_scratch_size(int n_cut, int m, int R, int num_spts);
 int hlgs_spt_cache_plan(const hlgs_cache_args* a, hlgs_cache_plan* plan, void* scratch, void* stream);
 /* dst_t[dst_rows[i]] = src_t[src_rows[i]] for i < n and every table t < T (at most 32); a NULL row list is the
- * identity.  row_bytes a multiple of 4; src / dst may be pinned host memory.  All of a cache step's parameter
+ * identity.  src_rows may be in any order and may repeat; dst_rows entries must be distinct.
+ * row_bytes a multiple of 4; src / dst may be pinned host memory.  All of a cache step's parameter
  * and Adam-moment traffic (train_post.py:439-479) in one launch per direction. */
 typedef struct hlgs_row_copy {
     const void* src;
